@@ -1,6 +1,7 @@
 """Benchmark: env-steps/s of the batched HIP USV step at 65 536 envs per GPU (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--env-id usv-simple]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 --gpus N without a launcher starts N rank processes itself (spawn_ranks: fresh interpreters, the
@@ -15,11 +16,22 @@ region (inputs resident in HBM).  Multi-GPU: one process per GPU, envs sharded b
 (env_id_offset = rank * N), no collective on the step path (weak scaling); the only
 collectives are the barrier and the max-over-ranks of the elapsed time.
 
-Warm-up: the W warm-up steps, then more untimed steps until --clock-warmup seconds have passed
-(the GPU clock ramps over the first few hundred milliseconds of work; a short --warmup would
-otherwise time a cold chip).  The line reports both counts.
+Warm-up: the W warm-up steps, then more untimed steps, about --clock-warmup seconds of them (the GPU
+clock ramps over the first few hundred milliseconds of work; a short --warmup would otherwise time a
+cold chip).  Their number is fixed by the arguments (clock_warmup_steps: that many seconds at the
+headline config's rate, 16 022 steps by default), not read off the clock, so the timed steps start
+from the same state, and consume the same actions, in every run and every build.  The line reports
+both counts.
 
-Rank 0 prints one JSON line: value = all ranks' env-steps / max-rank time, plus
+--dump-outputs DIR: after the timed steps, what the last timed step wrote (what a caller of usv_step
+receives) goes to DIR/obs.npy, reward.npy, terminated.npy, truncated.npy and final_obs.npy (float32;
+reward float64 with --precision f64; flags as 0/1; final_obs rows of envs that did not end in that step
+are unspecified by the ABI and written as 0).  When the arrays exceed DUMP_BYTES in all, the same
+seeded sample of env rows (dump_rows) is written for each.  With --gpus N > 1 rank r > 0 writes
+<name>.rank<r>.npy.
+
+A plain run does only the above.  Rank 0 prints one JSON line: value = all ranks' env-steps /
+max-rank time, plus
   roofline:     algorithmic bytes per launch / mean launch duration (HIP events on the env's stream
                 around groups of back-to-back launches 2..K; --event-layout edge: one pair around
                 all K launches, no timing marker between two launches)
@@ -27,6 +39,9 @@ Rank 0 prints one JSON line: value = all ranks' env-steps / max-rank time, plus
                 rocprofv3 PMC summary (profiles/pmc_summary.json) when it matches the workload;
                 valu_frac = VALU wave-instructions per launch (same summary, SQ_INSTS_VALU) x 2
                 cycles (a wave64 VALU instruction on a SIMD-32) / (1024 SIMDs x 2.4 GHz x launch time).
+--full adds the legs that take runs of their own (null in a plain run's line):
+  roofline.steady: one HIP event pair around --steady-steps more launches after the timed region.
+  f64:          the default float64 step kernel on the same env count and actions (--f64-steps).
   api_step:     the public UsvVectorEnv.step() (ctypes call, checks, output tensors) timed over the
                 same envs, copy=True (fresh output tensors) and copy=False (persistent buffers).
   cpu_baseline: the CPU oracle (per-env NumPy restatement of the reference step, oracle/) timed
@@ -50,6 +65,8 @@ for _p in (ROOT, os.path.join(ROOT, "gym-usv_amd")):
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level table)
 SIMDS, CLOCK_GHZ, VALU_CYCLES = 1024, 2.4, 2   # 256 CUs x 4 SIMD-32; max clock; wave64 VALU issue
 METRIC = "env-steps/sec at 65 536 parallel envs; 1/2/4/8 MI355X scaling"
+WARMUP_RATE = 3.5e9        # env-steps/s that sizes the clock warm-up (the headline config's, rounded)
+DUMP_BYTES = 60 << 20      # --dump-outputs writes at most this much array data (under 64 MB with the headers)
 
 
 # --------------------------------------------------------------------------- byte model
@@ -95,6 +112,12 @@ def reduce_max(values, device=None):
 def aggregate_rate(envs_per_rank, world, steps, max_elapsed):
     """Whole-job env-steps/s: every rank's env-steps over the slowest rank's time (weak scaling)."""
     return envs_per_rank * world * steps / max_elapsed
+
+
+def clock_warmup_steps(seconds, envs):
+    """Untimed steps that keep the GPU busy for about `seconds` at WARMUP_RATE (a slower config warms
+    up for longer): a function of the arguments alone."""
+    return math.ceil(seconds * WARMUP_RATE / envs) if seconds > 0 else 0
 
 
 def timed_window(launch, K, sync, barrier):
@@ -293,12 +316,17 @@ def parse_args(argv=None):
                     help="edge: one event pair around all K timed launches; mid: groups inside the loop")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_summary.json"))
     ap.add_argument("--clock-warmup", type=float, default=0.3,
-                    help="untimed steps after --warmup until this many seconds have passed")
+                    help="untimed steps after --warmup, this many seconds' worth at WARMUP_RATE")
     ap.add_argument("--steady-steps", type=int, default=1000,
                     help="untimed launches after the timed region for roofline.steady (0 = skip)")
     ap.add_argument("--f64-steps", type=int, default=500,
                     help="launches of the f64 (reference-precision) leg after the timed region (0 = skip)")
     ap.add_argument("--api-steps", type=int, default=200, help="steps of the public-API leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: roofline.steady, the f64 kernel, "
+                         "the public-API step and the CPU baseline (each still has its own switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
     ap.add_argument("--variant", default=None, help="step-kernel variant epb,lid,kind (tools; default: tuned)")
     return ap.parse_args(argv)
 
@@ -460,6 +488,14 @@ class StepWorkload:
     def event(self):
         return _StreamEvent(self.stream)
 
+    def outputs(self):
+        """What the last launch wrote, as {name: device tensor}; final_obs rows of envs that did not
+        end in that step hold whatever an earlier step (or the allocator) left there: zeroed here."""
+        import torch
+        done = (self.term | self.trunc).bool()
+        return {"obs": self.obs, "reward": self.rew, "terminated": self.term, "truncated": self.trunc,
+                "final_obs": torch.where(done[:, None], self.fobs, torch.zeros_like(self.fobs))}
+
     def extras(self):
         """The legs after the timed region, untimed by the contract: the f64 (reference-precision)
         kernel and the public-API step."""
@@ -496,6 +532,35 @@ class StepWorkload:
         self.env.close()
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+def dump_rows(n, row_bytes, budget=DUMP_BYTES):
+    """Env rows that --dump-outputs writes: all n when they fit the budget, else a sorted sample drawn
+    without replacement by numpy's default_rng(0) (the same rows in every run and every build)."""
+    import numpy as np
+    m = budget // row_bytes
+    if m >= n:
+        return None
+    return np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+
+
+def dump_outputs(outputs, out_dir, rank=0, budget=DUMP_BYTES):
+    """Write {name: device tensor [N, ...]} as out_dir/<name>.npy (float64 stays, everything else
+    float32), the same dump_rows of every array."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    width = {k: (8 if t.dtype == torch.float64 else 4) * (t[0].numel() if t.dim() > 1 else 1)
+             for k, t in outputs.items()}
+    n = len(next(iter(outputs.values())))
+    rows = dump_rows(n, sum(width.values()), budget)
+    for k, t in outputs.items():
+        if rows is not None:
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.cpu().numpy()
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        np.save(os.path.join(out_dir, f"{k}.npy" if rank == 0 else f"{k}.rank{rank}.npy"), a)
+
+
 # --------------------------------------------------------------------------- main
 def run(args, rank, world, local, workload_cls=None):
     """One rank of the bench: warm-up, the timed window, the kernel timing, the max over ranks; rank 0
@@ -510,14 +575,13 @@ def run(args, rank, world, local, workload_cls=None):
 
     for k in range(W):
         launch(k)
-    # clock warm-up (untimed): keep stepping until the GPU has been busy for --clock-warmup seconds
-    wl.sync()
-    extra, tw = 0, time.perf_counter()
-    while time.perf_counter() - tw < args.clock_warmup:
-        for _ in range(64):
-            launch(W + extra)
-            extra += 1
-        wl.sync()
+    # clock warm-up (untimed): more steps, about --clock-warmup seconds' worth; a count fixed by the
+    # arguments, not by the clock, so the timed steps start from the same state in every run
+    extra = clock_warmup_steps(args.clock_warmup, N)
+    for k in range(extra):
+        launch(W + k)
+        if k % 1024 == 1023:
+            wl.sync()                                 # (keeps the launch queue short)
     W2 = W + extra
     # HIP events on the env's stream bracket groups of G back-to-back launches (one event pair
     # per group; a pair around every single launch would add its own gap to each launch)
@@ -553,11 +617,13 @@ def run(args, rank, world, local, workload_cls=None):
         kern_ms = ev[0][0].elapsed_time(ev[0][1]) / K
     else:
         kern_ms = (sum(a.elapsed_time(b) for a, b in ev) / (groups * G)) if groups else elapsed / K * 1e3
+    if args.dump_outputs:
+        dump_outputs(wl.outputs(), args.dump_outputs, rank)
     # steady-state kernel time (after the timed region, untimed by the contract): one event pair
     # around --steady-steps more back-to-back launches, so the roofline is not read off a single
     # 16-launch group when the driver runs --steps 20
     steady_ms = None
-    if args.steady_steps > 0:
+    if args.full and args.steady_steps > 0:
         sa, sb = wl.event(), wl.event()
         sa.record()
         for k in range(args.steady_steps):
@@ -566,7 +632,7 @@ def run(args, rank, world, local, workload_cls=None):
         sb.synchronize()
         steady_ms = sa.elapsed_time(sb) / args.steady_steps
     elapsed, kern_ms, steady_ms = reduce_max([elapsed, kern_ms, steady_ms or 0.0], device=wl.collective_device)
-    legs = wl.extras()
+    legs = wl.extras() if args.full else {"f64": None, "api_step": None}
 
     out = None
     if rank == 0:
@@ -610,7 +676,7 @@ def run(args, rank, world, local, workload_cls=None):
         if args.env_id in LEGACY_IDS:
             out["config"].pop("lidar")
             out["config"].pop("mean_obstacles")
-        if not args.no_cpu_baseline and world == 1:        # the CPU leg runs at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:        # the CPU leg runs at N = 1 only
             cores, aff, quota = host_cores()
             out["cpu_baseline"] = cpu_baseline(args.env_id, args.cpu_seconds, args.cpu_procs or cores, aff, quota)
         else:

@@ -32,5 +32,5 @@ python3 tools/pmc_summary.py --kt $OUT/kt --fetch $OUT/fetch --write $OUT/write 
   --key $ENV_ID/$ENVS/$PREC/window --round $R --out $OUT/profiles ${KERNELS:+--kernels "$KERNELS"}
 find $OUT/kt -name "*kernel_stats.csv" -exec cp {} $OUT/profiles/${R}_kernel_stats.csv \;
 # bench last, with the default CPU leg at 65 536 envs: it reads roofline.traffic / valu_frac from the summary
-timeout -k 10 300 python bench.py --envs $ENVS --env-id $ENV_ID --precision $PREC --pmc $OUT/profiles/pmc_summary.json $([ "$ENVS" != 65536 ] && echo --no-cpu-baseline) > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full --envs $ENVS --env-id $ENV_ID --precision $PREC --pmc $OUT/profiles/pmc_summary.json $([ "$ENVS" != 65536 ] && echo --no-cpu-baseline) > $OUT/bench.json 2> $OUT/bench.err
 tail -1 $OUT/bench.json

@@ -14,7 +14,7 @@ rc=$?; echo "pytest rc $rc"; tail -3 $O/pytest_gpu.log; stop $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 rc=$?; echo "smoke rc $rc"; tail -2 $O/smoke.log; stop $rc
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_driver.$i.json 2> $O/bench_driver.$i.err
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver.$i.json 2> $O/bench_driver.$i.err
   rc=$?; echo "bench $i rc $rc"; stop $rc
 done
 bash tools/profile_round.sh $TAG > $O/prof.log 2>&1
