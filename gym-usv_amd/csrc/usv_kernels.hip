@@ -319,12 +319,12 @@ __device__ __forceinline__ void reset_experiment(const State<R>& S, int e, int e
   if (info) reset_info<R>(info, px, py, psi, u, v, r, ps0, ps1, pe0, pe1, ye, cdiv(angle, kPi));
 }
 
+// `ep` (wave-uniform): env e's episode counter, the Philox counter of this reset's draws
 template <typename R, int MODE>
-__device__ __forceinline__ void reset_wave(const State<R>& S, int e, float* row, R* info = nullptr,
-                                           int kpath = 0) {
+__device__ __forceinline__ void reset_wave_ep(const State<R>& S, int e, int ep, float* row, R* info = nullptr,
+                                              int kpath = 0) {
   if (S.np_reset) return;                  // NumPy-exact mode: np_autoreset_kernel resets after the step
   const int l = lane_id();
-  const int ep = uniform(S.I(I_EPISODE)[e]);
   Philox g(S.seed, S.gid0 + (uint64_t)e, (uint32_t)ep);
   Uni4<R> U;
   philox_uniforms(g, l, U);
@@ -406,6 +406,15 @@ __device__ __forceinline__ void reset_wave(const State<R>& S, int e, float* row,
     for (int i = 0; i < kHdr; ++i) row[i] = h[i];
     if (info) reset_info<R>(info, sx, sy, psi, u, v, r, sx, sy, sx + ca * dist, sy + sa * dist, R(0), cdiv(angle, kPi));
   }
+}
+
+// The same with the episode counter loaded here.  (The block-queue step passes its own, staged in LDS
+// before any store: this load, issued after a pair's stores, would wait for every one of their acks.)
+template <typename R, int MODE>
+__device__ __forceinline__ void reset_wave(const State<R>& S, int e, float* row, R* info = nullptr,
+                                           int kpath = 0) {
+  if (S.np_reset) return;
+  reset_wave_ep<R, MODE>(S, e, uniform(S.I(I_EPISODE)[e]), row, info, kpath);
 }
 
 // sin/cos of the heading used by the lidar; the step kernel and the reset kernel (stale scan)
@@ -2022,13 +2031,32 @@ __device__ __forceinline__ void q_emit_done(const State<float>& S, const IO<floa
   }
 }
 
+// The kernel's arguments for its rare paths (a done env's terminal obs, a same-step reset), re-read
+// from the kernarg segment where such a path begins.  The pointer passes through an empty asm, so
+// the compiler cannot tell the copy from a fresh load: what the rare path derives from State / IO
+// (the Philox key schedule, every field's base pointer, fobs, sensor_last) is then computed inside
+// it, not hoisted ahead of the pair loop and carried through it in registers ("Cold
+// paths").  Scalar loads: they count on lgkmcnt and wait for no store.  For kernels whose
+// parameters are exactly (State<float>, IO<float>).
+constexpr double kQRare = 1.0 - 1e-6;   // branch weight of the pair loop's rare paths
+struct QColdArgs { State<float> S; IO<float> io; };
+static_assert(sizeof(State<float>) % alignof(IO<float>) == 0, "IO follows State in the kernarg segment");
+__device__ __forceinline__ QColdArgs q_cold_args() {
+  typedef const __attribute__((address_space(4))) QColdArgs* KArg;   // (typed: 8-B aligned scalar loads)
+  KArg ka = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  QColdArgs c;
+  __builtin_memcpy(&c, ka, sizeof(c));
+  return c;
+}
+
 // Two block shapes: QE = 128 envs on QW = 16 waves (the default, two blocks per CU), and QE = 16 envs
 // on QW = 8 waves for small env counts, where 128-env blocks would leave most CUs idle (4 096 envs
 // are 32 such blocks) -- each wave then owns about one pair, and up to four blocks share a CU.
 constexpr int kQE_S = 16, kQW_S = 8;
 constexpr int kQSmallBelow = 32768;   // env count below which the small blocks are the default (tools/nsweep.sh)
 template <int QE = kQE, int QW = kQW> __host__ __device__ constexpr size_t lds_q_bytes() {
-  return wave_tab_bytes<float>() + QW * q_slice_bytes() + QE * kQRec * 4 + 16 + QE * 4;   // + n_obs[QE]
+  return wave_tab_bytes<float>() + QW * q_slice_bytes() + QE * kQRec * 4 + 16 + 2 * QE * 4;   // + n_obs[QE], episode[QE]
 }
 static_assert(2 * lds_q_bytes() <= 160 * 1024, "two blocks per CU");
 static_assert(4 * lds_q_bytes<kQE_S, kQW_S>() <= 160 * 1024, "four small blocks per CU");
@@ -2058,6 +2086,7 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
   float* const recs = reinterpret_cast<float*>(lds + wave_tab_bytes<float>() + kQW * q_slice_bytes());
   unsigned* const qctr = reinterpret_cast<unsigned*>(recs + kQE * kQRec);
   int* const qnob = reinterpret_cast<int*>(recs + kQE * kQRec) + 4;   // fused: the block's n_obs
+  int* const qep = qnob + kQE;                                        // the block's episode counters
   const float2* const rayoff = reinterpret_cast<const float2*>(lds);
 #ifdef USV_DIAG_QPROF
   QProf qprof;
@@ -2097,14 +2126,26 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
       dma_copy1(S.orow(eb + 2 * w), lds + wave_tab_bytes<float>() + w * q_slice_bytes() + 256 * 8 + 64 * 4,
                 min(2, nbe - 2 * w) * rowb);
   }
-  if constexpr (FUSED) {
-    // the block's obstacle counts into LDS by waves 2 kDynWaves .. 3 kDynWaves - 1 (one env per lane),
-    // so the dynamics waves load nothing after their stores: a load issued after them would make the
-    // wave wait for every store's ack (one vmcnt counter) before the barrier
-    if (wave >= 2 * kDynWaves && wave < 3 * kDynWaves) {
-      const int k = (wave - 2 * kDynWaves) * kWave + l;
-      if (k < nbe) qnob[k] = S.I(I_NOBS)[eb + k];
+  {
+    // the block's obstacle counts (fused) and episode counters into LDS, one env per lane.  Fused: by
+    // waves 2 kDynWaves .. 3 kDynWaves - 1, so the dynamics waves load nothing after their stores: a
+    // load issued after them would make the wave wait for every store's ack (one vmcnt counter)
+    // before the barrier.  Split: by the waves below the ray table's, which copy no records.
+    // The episode counters are for the same-step resets after the pair loop: an env is reset at most
+    // once per launch, so the staged counter is its current one, and the reset starts with no load
+    // queued behind its wave's stores.
+    constexpr int kStageWaves = (kQE + kWave - 1) / kWave;
+    constexpr int kStage0 = FUSED ? 2 * kDynWaves : kQW - 1 - kStageWaves;
+    static_assert(kStage0 >= kDynWaves && kStage0 + kStageWaves <= kQW, "staging waves");
+    if (wave >= kStage0 && wave < kStage0 + kStageWaves) {
+      const int k = (wave - kStage0) * kWave + l;
+      if (k < nbe) {
+        if constexpr (FUSED) qnob[k] = S.I(I_NOBS)[eb + k];
+        qep[k] = S.I(I_EPISODE)[eb + k];
+      }
     }
+  }
+  if constexpr (FUSED) {
     // dynamics, one lane per env.  Lanes past the end repeat the wave's last env (same wave:
     // every lane loads the state before any lane stores it); a wave with no env of its own must
     // not run, or two waves would race on the same env's state
@@ -2127,6 +2168,29 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
   }
   // rows, ray table and records landed (the dynamics waves issued no DMA: their stores drain later,
   // ahead of their first pair's rows in the vmcnt order)
+  // Per-lane and per-block invariants of the pair loop that do not depend on phase 1, computed (and
+  // pinned: the compiler otherwise sinks them to the loop's preheader) ahead of the barrier by the
+  // waves that only wait there; the dynamics waves, which the barrier waits for, do it after it.
+  // hpk: the per-row layout's obs-header lanes (SPAN = false), loop-invariant, packed in one register:
+  // lanes 0..14 store env A's header value hi, 15..29 env B's, 30..63 repeat lane 29; the record slot
+  // of value hi (qrec_hdr) in bits 8..12, bit 16: env B's lane, bit 17: a constant entry (1, 10, 12-14).
+  // oblk: this block's obstacle rows (pair p at 2 p rowb bytes).  ob: see pair_shift below.
+  int hpk = 0;
+  const float* oblk = nullptr;
+  unsigned ob = 0;
+  auto loop_setup = [&] {
+    if constexpr (!SPAN) {
+      const int hl = min(l, 2 * kHdr - 1);
+      const int hi = hl >= kHdr ? hl - kHdr : hl;
+      const int hrec = hi == 0 ? 6 : (hi <= 9 ? hi + 5 : 15);
+      hpk = hi | (hrec << 8) | ((hl >= kHdr) << 16) | ((hi == 1 || hi == 10 || hi >= 12) << 17);
+      asm volatile("" : "+v"(hpk));
+    }
+    oblk = S.orow(eb);
+    ob = (unsigned)(((uintptr_t)io.obs >> 2) & 7);
+    asm volatile("" : "+s"(oblk), "+s"(ob));
+  };
+  if (wave >= kDynWaves) loop_setup();
   USV_STAMP_W(1);
   if (wave >= kDynWaves) vm_wait<0>();
   QMARK(10);
@@ -2144,6 +2208,7 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
   if (FUSED && wave < kDynWaves) {
     vm_wait<0>();
     __hip_atomic_store(qdyn + wave, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    loop_setup();
   }
   USV_STAMP_W(2);
   QMARK(0);
@@ -2157,24 +2222,12 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
 #endif
   const bool hb = l >= 32;
   auto pair_hasb = [&](int p) { return 2 * p + 1 < nbe; };
-  const float* const oblk = S.orow(eb);               // this block's obstacle rows (pair p at 2 p rowb bytes)
 
   // An env pair's two obs rows are one 1144-B span, stored as five 256-B wave stores from the span's
   // first 32-B sector: every sector but the two at the span's ends is written whole by one write-through
   // store (the four sensor halves and the header store of round 3 split ~3 sectors per row between
   // instructions, 1.18x the algorithmic write bytes).  sh = the span's dword offset in its sector.
-  const unsigned ob = (unsigned)(((uintptr_t)io.obs >> 2) & 7);
   auto pair_shift = [&](int p) { return (int)((ob + (unsigned)(eb + 2 * p) * (unsigned)kObsDim) & 7u); };
-  // per-row layout (SPAN = false): the obs-header lanes are loop-invariant, packed in one register:
-  // lanes 0..14 store env A's header value hi, 15..29 env B's, 30..63 repeat lane 29; the record slot
-  // of value hi (qrec_hdr) in bits 8..12, bit 16: env B's lane, bit 17: a constant entry (1, 10, 12-14)
-  int hpk = 0;
-  if constexpr (!SPAN) {
-    const int hl = min(l, 2 * kHdr - 1);
-    const int hi = hl >= kHdr ? hl - kHdr : hl;
-    const int hrec = hi == 0 ? 6 : (hi <= 9 ? hi + 5 : 15);
-    hpk = hi | (hrec << 8) | ((hl >= kHdr) << 16) | ((hi == 1 || hi == 10 || hi >= 12) << 17);
-  }
   // env record of pair c for this lane (lanes 0..31 env A, 32..63 env B; env A again when there is
   // no B): pose, meta and the obs-header value this lane stores (lanes sh..sh+14: env A's entries
   // 0..14, sh+15..sh+29: env B's; no env B: sh = 0 and lanes 15..29 repeat env A's).  Read one pair
@@ -2291,9 +2344,10 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
       if constexpr (DONE) io.done[el] = done_l;        // (>= 7 stores still follow the DMA)
       const unsigned long long dm = ballot(done_l);
       const bool doneA = (unsigned)dm != 0u, doneB = hasB && (unsigned)(dm >> 32) != 0u;
-      if (doneA | doneB) {
-        if (doneA) q_emit_done(S, io, e0, sa, recs + k0 * kQRec, rotA);
-        if (doneB) q_emit_done(S, io, e0 + 1, sb, recs + (k0 + 1) * kQRec, rotB);
+      if (__builtin_expect_with_probability(doneA | doneB, 0, kQRare)) {
+        const QColdArgs c = q_cold_args();
+        if (doneA) q_emit_done(c.S, c.io, e0, sa, recs + k0 * kQRec, rotA);
+        if (doneB) q_emit_done(c.S, c.io, e0 + 1, sb, recs + (k0 + 1) * kQRec, rotB);
       }
       // the next pair's rows landed: at least seven stores (four sensor halves, the headers, the
       // rewards and the terminated flags) were issued after their DMA
@@ -2306,14 +2360,15 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
       meta = meta_n;
       hv = hv_n;
       ++it;
-      if (S.autoreset == USV_AUTORESET_SAME_STEP && (doneA | doneB)) {
+      if (__builtin_expect_with_probability(S.autoreset == USV_AUTORESET_SAME_STEP && (doneA | doneB), 0, kQRare)) {
         done = (doneA ? 1u : 0u) | (doneB ? 2u : 0u);
         de0 = e0;
         break;
       }
     }
-    if (!done) break;
+    if (__builtin_expect(!done, 1)) break;
     QMARK(11);
+    const QColdArgs c = q_cold_args();
     for (; done; done &= done - 1) {
       const int e = de0 + __builtin_ctz(done);
       if constexpr (FUSED) {
@@ -2323,7 +2378,7 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
         while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u)
           __builtin_amdgcn_s_sleep(2);
       }
-      reset_wave<float, MODE>(S, e, io.obs + (size_t)e * kObsDim);
+      reset_wave_ep<float, MODE>(c.S, e, uniform(qep[e - eb]), c.io.obs + (size_t)e * kObsDim);
     }
     QMARK(7);
   }

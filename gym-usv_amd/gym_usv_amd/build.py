@@ -18,7 +18,14 @@ ARCH = os.environ.get("USV_OFFLOAD_ARCH", "gfx950")
 # The block-queue step takes its next pair's LDS ticket one pair ahead; the atomic optimizer would
 # rewrite that single-lane atomicAdd into a wave reduction whose result is consumed at once, exposing
 # the LDS atomic's latency every pair.
-DEVICE_FLAGS = ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
+#
+# The block-queue step's rare paths (a done env's terminal obs, a same-step reset) sit inside its
+# loops, and machine LICM hoists their literals (the reset's 2 pi, NaN, polynomial coefficients, the
+# Philox multipliers: sixteen VGPRs) ahead of the pair loop, which then carries them.  The last two
+# options keep an instruction in its block when the loop's preheader runs more often than that block
+# (static block frequencies; the rare branches carry their probability in the source).
+DEVICE_FLAGS = ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None",
+                "-mllvm", "-disable-hoisting-to-hotter-blocks=all", "-mllvm", "-block-freq-ratio-threshold=1"]
 
 
 def hipcc():

@@ -7,6 +7,7 @@ mkdir -p diagbuild
 for x in "$@"; do
   lc=$(echo $x | tr A-Z a-z)
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -mllvm -amdgpu-atomic-optimizer-strategy=None \
+    -mllvm -disable-hoisting-to-hotter-blocks=all -mllvm -block-freq-ratio-threshold=1 \
     -Iinclude -DUSV_DIAG -DUSV_DIAG_$x -o diagbuild/$lc.so gym-usv_amd/csrc/usv_kernels.hip &
 done
 wait

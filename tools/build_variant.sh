@@ -6,4 +6,5 @@ cd "$(dirname "$0")/.."
 mkdir -p diagbuild
 n=$1; shift
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -mllvm -amdgpu-atomic-optimizer-strategy=None \
+  -mllvm -disable-hoisting-to-hotter-blocks=all -mllvm -block-freq-ratio-threshold=1 \
   -Iinclude "$@" -o diagbuild/$n.so gym-usv_amd/csrc/usv_kernels.hip

@@ -51,7 +51,8 @@ def main():
     args = ap.parse_args()
     src = os.path.join(ROOT, "gym-usv_amd", "csrc", "usv_kernels.hip")
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S",
-                    "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-I" + os.path.join(ROOT, "include"),
+                    "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-mllvm", "-disable-hoisting-to-hotter-blocks=all",
+                    "-mllvm", "-block-freq-ratio-threshold=1", "-I" + os.path.join(ROOT, "include"),
                     "-DUSV_DIAG", "-DUSV_DIAG_SECTIONS", *os.environ.get("XDEFS", "").split(), "-o", args.asm, src], check=True,
                    stderr=subprocess.DEVNULL)
     t = open(args.asm).read()
