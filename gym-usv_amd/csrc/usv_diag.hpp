@@ -1,13 +1,17 @@
-// usv_diag.hpp -- instrumentation of the DIAGNOSTIC builds only (tools/build_diag.sh: -DUSV_DIAG
-// plus one of USV_DIAG_STAMPS / USV_DIAG_PROF / USV_DIAG_QPROF).  The product library never
-// includes this file: usv_kernels.hip defines the same names as no-ops when USV_DIAG is unset.
-// Stamps go to __device__ arrays of their own that no kernel output reads.
+// usv_diag.hpp -- instrumentation of the DIAGNOSTIC builds (tools/build_diag.sh: -DUSV_DIAG plus one
+// of USV_DIAG_STAMPS / USV_DIAG_PROF / USV_DIAG_QPROF / USV_DIAG_SECTIONS).  Without them, as in the
+// product library, every name here is a no-op.  Stamps go to __device__ arrays of their own that no
+// kernel output reads.
 #pragma once
-#ifndef USV_DIAG
-#error "usv_diag.hpp is for the diagnostic builds only (-DUSV_DIAG)"
+
+#include <hip/hip_runtime.h>
+
+#if !defined(USV_DIAG) && (defined(USV_DIAG_STAMPS) || defined(USV_DIAG_PROF) || defined(USV_DIAG_QPROF) || \
+                           defined(USV_DIAG_SECTIONS))
+#error "the USV_DIAG_* switches are for the diagnostic builds only (-DUSV_DIAG)"
 #endif
 
-// (included inside namespace usv by usv_kernels.hip)
+namespace usv {
 
 // Diagnostic build only (-DUSV_DIAG_STAMPS): per-block s_memrealtime (100 MHz) stamps at the
 // phase boundaries of the step kernel, read back with usv_diag_stamps().  Never in the product.
@@ -19,13 +23,7 @@ __device__ unsigned long long g_stamps[32768 * kStampSlots];
     if (threadIdx.x == 0 && blockIdx.x < 32768)                                           \
       g_stamps[blockIdx.x * kStampSlots + (i)] = __builtin_amdgcn_s_memrealtime();        \
   } while (0)
-// block slot, written by the first lane of whichever wave executes it (kind 0)
-#define USV_STAMP_B(i)                                                                    \
-  do {                                                                                    \
-    if ((threadIdx.x & 63) == 0 && blockIdx.x < 32768)                                    \
-      g_stamps[blockIdx.x * kStampSlots + (i)] = __builtin_amdgcn_s_memrealtime();        \
-  } while (0)
-// wave slot (global wave index; kinds 1-3)
+// wave slot (global wave index; the wave-per-env step)
 #define USV_STAMP_W(i)                                                                    \
   do {                                                                                    \
     const unsigned gw_ = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;               \
@@ -49,7 +47,6 @@ __device__ unsigned long long g_stamps[32768 * kStampSlots];
 #else
 #define USV_STAMP_ID() do {} while (0)
 #define USV_STAMP(i) do {} while (0)
-#define USV_STAMP_B(i) do {} while (0)
 #define USV_STAMP_W(i) do {} while (0)
 #define USV_STAMP_V(i, v) do {} while (0)
 #endif
@@ -113,3 +110,5 @@ struct QProf { __device__ void mark(int) {} __device__ void count(int, unsigned 
 #define QCOUNT(i, k) do {} while (0)
 __device__ __forceinline__ void qprof_flush(QProf*) {}
 #endif
+
+}  // namespace usv

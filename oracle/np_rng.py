@@ -1,5 +1,5 @@
 """Pure-Python restatement of the NumPy Generator(PCG64) draws the reference's reset makes —
-TEST INFRASTRUCTURE (checks the device-side NumPy-exact reset, gym-usv_amd/csrc/usv_kernels.hip
+TEST INFRASTRUCTURE (checks the device-side NumPy-exact reset, gym-usv_amd/csrc/usv_reset.hpp
 `NpPcg64`, and is itself checked against numpy in tests/test_np_rng.py).
 
 Algorithms (numpy 2.x, numpy/random/src): PCG64 = 128-bit LCG with the XSL-RR output, stepped

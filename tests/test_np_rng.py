@@ -51,7 +51,7 @@ def test_np_rng_words_layout():
 
 
 def np_reset_py(g):
-    """Statement-for-statement mirror of the device np_reset (usv_kernels.hip)."""
+    """Statement-for-statement mirror of the device np_reset (usv_reset.hpp)."""
     kb = 20.0
     sx = 0.5 * g.standard_normal() + kb / 2
     sy = 0.5 * g.standard_normal() + kb / 2

@@ -1,6 +1,6 @@
 # Diagnostic builds of the step library (never the product): clock stamps / section counters.
 #   bash tools/build_diag.sh STAMPS QPROF PROF   -> diagbuild/stamps.so, diagbuild/qprof.so, diagbuild/prof.so (travels with gpurun)
-# Each defines USV_DIAG (csrc/usv_diag.hpp is included only then) plus USV_DIAG_<X>.
+# Each defines USV_DIAG (csrc/usv_diag.hpp is no-ops without it) plus USV_DIAG_<X>.
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p diagbuild
