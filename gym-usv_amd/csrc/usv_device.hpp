@@ -13,6 +13,8 @@
 
 #include <type_traits>
 
+#include "usv_layout.hpp"   // kSensors, kAsmcN and the other constants of the state layout
+
 // No implicit a*b+c contraction anywhere in the device code: every fused multiply-add is an
 // explicit m_fma/fmaf.  With contraction left to the backend, the same inlined function can
 // round differently in different kernels (it depends on the surrounding code), and the step
@@ -22,10 +24,8 @@
 namespace usv {
 
 // ----------------------------------------------------------------------------- constants
-constexpr int kSensors = 128;                      // simple_env.py:11
 constexpr int kObsDim = 143;                       // simple_env.py:27
 constexpr int kHdr = 15;                           // obs[0:15] (simple_env.py:96)
-constexpr int kAsmcN = 16;                         // unique UsvAsmc state values
 constexpr int kWave = 64;
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kSensorMax = 100.0;               // simple_env.py:13

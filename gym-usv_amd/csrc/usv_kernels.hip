@@ -1,8 +1,9 @@
 // usv_kernels.hip -- host side and C ABI (include/usv_hip.h) of the batched USV path-following
 // environment for gfx950.  The single translation unit of the library; the device code lives in
 // the headers it includes, in this order:
-//   usv_device.hpp        constants, math shims, wave helpers, Philox, the ASMC substep
 //   usv_variant.hpp       step-variant kinds, block shapes and rules (host C++, no HIP)
+//   usv_layout.hpp        state layout: constants, the slab's regions, the field table (host C++, no HIP)
+//   usv_device.hpp        constants, math shims, wave helpers, Philox, the ASMC substep
 //   usv_diag.hpp          instrumentation of the diagnostic builds, no-ops in the product
 //   usv_state.hpp         State / IO, fields, heading frame, output stores, obs header
 //   usv_reset.hpp         Philox / experiment / NumPy-exact resets, autoreset kernels
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "usv_hip.h"
@@ -54,14 +56,6 @@ int fail(int code, const std::string& msg) {
       return fail(USV_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(_e));      \
   } while (0)
 
-struct FieldDesc { const char* name; int is_int; };
-const FieldDesc kFields[USV_FIELD_COUNT] = {
-    {"x", 0}, {"y", 0}, {"psi", 0}, {"u", 0}, {"v", 0}, {"r", 0}, {"last_u", 0}, {"last_r", 0},
-    {"progress", 0}, {"path_x0", 0}, {"path_y0", 0}, {"path_x1", 0}, {"path_y1", 0},
-    {"max_u", 0}, {"max_r", 0}, {"ref_v", 0}, {"n_obs", 1}, {"elapsed", 1}, {"episode", 1},
-    {"scan_valid", 1}, {"obs_x", 0}, {"obs_y", 0}, {"obs_r", 0}, {"sensor_last", 0}, {"asmc", 0},
-    {"v0_last", 0}, {"v0_aux", 0}, {"v0_target", 0}, {"v0_action_last", 0}, {"v0_ye", 0}, {"np_rng", 1}, {"np_mt", 1}};
-
 struct Handle {
   usv_config cfg;
   int device;
@@ -69,18 +63,22 @@ struct Handle {
   int kind = 0, epb = 0, lid = 0;
   int cus = 256;                       // compute units of the device (State::qyoung)
   void* slab = nullptr;
+  SlabLayout lay{};                    // the slab's regions and the public fields in them (usv_layout.hpp)
+  FieldTable fields{};
   void* exp_buf = nullptr;             // device usv_experiment record (kExp* layout, in R)
-  State<float> sf{};
-  State<double> sd{};
+  std::variant<State<float>, State<double>> st;   // by cfg.precision (usv_create)
 };
+
+// f(S) with the handle's state, State<float> or State<double>
+template <typename F>
+auto with_state(Handle* h, F&& f) { return std::visit(f, h->st); }
 
 // Installs a step variant (default_variant / variant_allowed): the only writer of these members.
 void apply_variant(Handle* h, const Variant& v) {
   h->kind = v.kind;
   h->epb = v.epb;
   h->lid = v.lid;
-  h->sf.prio = h->sd.prio = v.prio;
-  h->sf.rowspan = h->sd.rowspan = v.rowspan;
+  with_state(h, [&](auto& S) { S.prio = v.prio; S.rowspan = v.rowspan; });
 }
 
 struct DeviceGuard {
@@ -97,36 +95,29 @@ struct DeviceGuard {
 
 template <typename R>
 int carve(Handle* h, State<R>& S) {
-  const size_t N = (size_t)h->cfg.num_envs, cap = (size_t)h->cfg.obstacle_cap;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t stride = al(N * sizeof(R)) / sizeof(R);   // also >= N int32 (sizeof(R) >= 4)
-  const size_t bytes = F_NREAL * stride * sizeof(R) + al(I_NINT * stride * 4) +
-                       al(N * 3 * obst_stride((int)cap) * sizeof(R)) + al(N * kSensors * sizeof(R)) +
-                       al((size_t)kAsmcN * N * sizeof(R)) + al((size_t)kV0N * stride * sizeof(R)) +
-                       al(2 * kSensors * sizeof(R)) + al(2 * N * sizeof(R4<R>)) + al(10 * stride * 4) +
-                       al((kExpObs + 3 * cap) * sizeof(R)) + al(N * kQRec * sizeof(float)) +
-                       (is_legacy(h->cfg.mode) ? al(625 * stride * 4) : 0);
-  HIP_TRY(hipMalloc(&h->slab, bytes));
-  HIP_TRY(hipMemset(h->slab, 0, bytes));
-  char* p = (char*)h->slab;
-  auto take = [&](size_t b) { char* q = p; p += al(b); return (void*)q; };
-  S.freal = (R*)take(F_NREAL * stride * sizeof(R));
-  S.fint = (int32_t*)take(I_NINT * stride * 4);
-  S.fstride = (int)stride;
-  S.ostride = obst_stride((int)cap);
-  S.obst = (R*)take(N * 3 * S.ostride * sizeof(R));
-  S.sensor_last = (R*)take(N * kSensors * sizeof(R));
-  S.asmc = (R*)take((size_t)kAsmcN * N * sizeof(R));
-  S.v0 = (R*)take((size_t)kV0N * stride * sizeof(R));
-  R* tab = (R*)take(2 * kSensors * sizeof(R));
+  const size_t N = (size_t)h->cfg.num_envs;
+  const SlabLayout& L = h->lay = slab_layout(h->cfg, sizeof(R));
+  h->fields = field_table(h->cfg, L);
+  HIP_TRY(hipMalloc(&h->slab, L.total));
+  HIP_TRY(hipMemset(h->slab, 0, L.total));
+  auto at = [&](Region r) { return L.size[r] ? (void*)((char*)h->slab + L.off[r]) : nullptr; };
+  S.freal = (R*)at(R_FREAL);
+  S.fint = (int32_t*)at(R_FINT);
+  S.fstride = (int)L.fstride;
+  S.ostride = (int)L.ostride;
+  S.obst = (R*)at(R_OBST);
+  S.sensor_last = (R*)at(R_SENSOR_LAST);
+  S.asmc = (R*)at(R_ASMC);
+  S.v0 = (R*)at(R_V0);
+  R* tab = (R*)at(R_RAY_TAB);
   S.ray_tab = tab;
-  S.pose = (R4<R>*)take(2 * N * sizeof(R4<R>));
-  S.qrec = (float*)take(N * kQRec * sizeof(float));
-  S.nprng = (uint32_t*)take(10 * stride * 4);
-  h->exp_buf = take((kExpObs + 3 * cap) * sizeof(R));
+  S.pose = (R4<R>*)at(R_POSE);
+  S.qrec = (float*)at(R_QREC);
+  S.nprng = (uint32_t*)at(R_NPRNG);
+  h->exp_buf = at(R_EXP);
   S.exp = nullptr;                                       // usv_set_experiment installs it
   S.perturb = (h->cfg.flags & USV_FLAG_PERTURB) != 0;
-  S.npmt = is_legacy(h->cfg.mode) ? (uint32_t*)take(625 * stride * 4) : nullptr;   // legacy ids only
+  S.npmt = (uint32_t*)at(R_NPMT);                        // legacy ids only, else null
   S.np_reset = 0;
   S.N = h->cfg.num_envs;
   S.cap = h->cfg.obstacle_cap;
@@ -238,11 +229,11 @@ QPick q_pick(int mode, int kind, int epb) {
 }
 // ... of one launch: the outputs the caller asked for, and the handle's row-store layout
 template <typename R>
-QPick q_pick(const Handle* h, const IO<R>& io) {
+QPick q_pick(const Handle* h, const State<R>& S, const IO<R>& io) {
   QPick q = q_pick(h->cfg.mode, h->kind, h->epb);
   q.done = io.done != nullptr;
   q.info = io.info != nullptr;
-  q.span = h->sf.rowspan != 0;
+  q.span = S.rowspan != 0;
   return q;
 }
 // ... and every choice a handle of this mode and kind can come to launch (usv_set_kernel_variant
@@ -314,7 +305,7 @@ int launch_step_kernels(Handle* h, State<R>& S, const float* act, float* obs, vo
       }
       if (h->kind == kQueueChain)                            // usv-asmc-simple: the ASMC chain first
         HIP_TRY(hipLaunchKernel((void*)&asmc_chain_kernel<float>, dim3((S.N + kBlock - 1) / kBlock), dim3(kBlock), args, 0, st));
-      const QPick q = q_pick(h, io);
+      const QPick q = q_pick(h, S, io);
       const int qe = q.small ? kQE_S : kQE, qw = q.small ? kQW_S : kQW;
       // a one-round grid of the 128-env blocks: the second block of each CU raises priority
       const int nblk = (S.N + qe - 1) / qe;
@@ -366,37 +357,6 @@ int launch_reset(Handle* h, State<R>& S, const uint8_t* mask, float* obs, int kp
   return USV_OK;
 }
 
-int field_per_env(const Handle* h, int f) {
-  if (f >= USV_FIELD_OBS_X && f <= USV_FIELD_OBS_R) return h->cfg.obstacle_cap;
-  if (f == USV_FIELD_SENSOR_LAST) return kSensors;
-  if (f == USV_FIELD_ASMC) return kAsmcN;
-  if (f == USV_FIELD_V0_LAST) return 9;
-  if (f == USV_FIELD_V0_AUX) return 3;
-  if (f == USV_FIELD_V0_TARGET) return 6;
-  if (f == USV_FIELD_V0_YE) return 2;
-  if (f == USV_FIELD_NP_RNG) return 10;
-  if (f == USV_FIELD_NP_MT) return is_legacy(h->cfg.mode) ? 625 : 0;
-  return 1;
-}
-
-// first v0 SoA row of a v0 field
-int v0_base(int f) {
-  return f == USV_FIELD_V0_LAST ? kV0Last : f == USV_FIELD_V0_AUX ? kV0Aux
-       : f == USV_FIELD_V0_TARGET ? kV0Target : f == USV_FIELD_V0_YE ? kV0Ye : kV0ALast;
-}
-
-// host <-> device for one field; host side [N][per] float64 / int32
-template <typename R>
-int field_io_impl(Handle* h, State<R>& S, int f, void* host, bool to_host);
-// Writes complete before returning (hipMemcpy from pageable memory may return before the DMA
-// lands), so a kernel the caller launches next on any stream sees them.
-template <typename R>
-int field_io(Handle* h, State<R>& S, int f, void* host, bool to_host) {
-  HIP_TRY(hipDeviceSynchronize());
-  const int rc = field_io_impl(h, S, f, host, to_host);
-  if (rc == USV_OK && !to_host) HIP_TRY(hipDeviceSynchronize());
-  return rc;
-}
 // f32 usv-simple / usv-asmc-simple keep the heading as phi + 2 pi k (store_heading): the host sees
 // and sets the reference's heading, and UsvAsmc's psi_d_last in the reference's frame.
 template <typename R>
@@ -449,114 +409,53 @@ int heading_io(Handle* h, State<R>& S, int f, double* hd, bool to_host) {
   return USV_OK;
 }
 
+// The one copy routine: gathers a field from its region (dev: the field's first element, T = R or
+// int32) into host [N][per] (H = double or int32), or scatters host into it.  The field's span of
+// the region is moved whole; where the span holds other data too (the obstacle planes, padded SoA
+// rows), a set is a read-modify-write.
+template <typename T, typename H>
+int copy_field(T* dev, const Field& fd, size_t N, H* host, bool to_host) {
+  const size_t per = (size_t)fd.per;
+  if (!per) return USV_OK;
+  const size_t span = (N - 1) * fd.env_stride + (per - 1) * fd.comp_stride + 1;
+  std::vector<T> tmp(span);
+  if (to_host || span != N * per) HIP_TRY(hipMemcpy(tmp.data(), dev, span * sizeof(T), hipMemcpyDeviceToHost));
+  for (size_t e = 0; e < N; ++e)
+    for (size_t c = 0; c < per; ++c) {
+      T& v = tmp[e * fd.env_stride + c * fd.comp_stride];
+      if (to_host) host[e * per + c] = (H)v;
+      else v = (T)host[e * per + c];
+    }
+  if (!to_host) HIP_TRY(hipMemcpy(dev, tmp.data(), span * sizeof(T), hipMemcpyHostToDevice));
+  return USV_OK;
+}
+
+// host <-> device for one field; host side [N][per] float64 / int32
 template <typename R>
 int field_io_impl(Handle* h, State<R>& S, int f, void* host, bool to_host) {
   const size_t N = (size_t)S.N;
   if (f == USV_FIELD_PSI && turn_frame<R>(h)) return heading_io<R>(h, S, f, (double*)host, to_host);
-  if (f < F_NREAL) {
-    std::vector<R> tmp(N);
-    double* hd = (double*)host;
-    if (to_host) {
-      HIP_TRY(hipMemcpy(tmp.data(), S.F(f), N * sizeof(R), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < N; ++i) hd[i] = (double)tmp[i];
-    } else {
-      for (size_t i = 0; i < N; ++i) tmp[i] = (R)hd[i];
-      HIP_TRY(hipMemcpy(S.F(f), tmp.data(), N * sizeof(R), hipMemcpyHostToDevice));
-    }
-    return USV_OK;
+  if (f == USV_FIELD_N_OBS && !to_host) {
+    const int32_t* hv = (const int32_t*)host;
+    for (size_t i = 0; i < N; ++i)
+      if (hv[i] < 0 || hv[i] > S.cap) return fail(USV_ERR_ARG, "n_obs out of [0, obstacle_cap]");
   }
-  if (f >= USV_FIELD_N_OBS && f <= USV_FIELD_SCAN_VALID) {
-    int32_t* d = S.I(f - USV_FIELD_N_OBS);
-    if (!to_host && f == USV_FIELD_N_OBS) {
-      const int32_t* hv = (const int32_t*)host;
-      for (size_t i = 0; i < N; ++i)
-        if (hv[i] < 0 || hv[i] > S.cap) return fail(USV_ERR_ARG, "n_obs out of [0, obstacle_cap]");
-    }
-    if (to_host) HIP_TRY(hipMemcpy(host, d, N * 4, hipMemcpyDeviceToHost));
-    else HIP_TRY(hipMemcpy(d, host, N * 4, hipMemcpyHostToDevice));
-    return USV_OK;
-  }
-  if (f >= USV_FIELD_OBS_X && f <= USV_FIELD_OBS_R) {   // device [N][3][ostride], host [N][cap]
-    const size_t os = (size_t)S.ostride, cnt = N * 3 * os, cap = (size_t)S.cap;
-    std::vector<R> tmp(cnt);
-    HIP_TRY(hipMemcpy(tmp.data(), S.obst, cnt * sizeof(R), hipMemcpyDeviceToHost));
-    double* hd = (double*)host;
-    const size_t plane = (size_t)(f - USV_FIELD_OBS_X);   // x / y / r
-    for (size_t e = 0; e < N; ++e)
-      for (size_t j = 0; j < cap; ++j) {
-        R& v = tmp[(e * 3 + plane) * os + j];
-        if (to_host) hd[e * cap + j] = (double)v;
-        else v = (R)hd[e * cap + j];
-      }
-    if (!to_host) HIP_TRY(hipMemcpy(S.obst, tmp.data(), cnt * sizeof(R), hipMemcpyHostToDevice));
-    return USV_OK;
-  }
-  if (f == USV_FIELD_SENSOR_LAST) {
-    const size_t cnt = N * kSensors;
-    std::vector<R> tmp(cnt);
-    double* hd = (double*)host;
-    if (to_host) {
-      HIP_TRY(hipMemcpy(tmp.data(), S.sensor_last, cnt * sizeof(R), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < cnt; ++i) hd[i] = (double)tmp[i];
-    } else {
-      for (size_t i = 0; i < cnt; ++i) tmp[i] = (R)hd[i];
-      HIP_TRY(hipMemcpy(S.sensor_last, tmp.data(), cnt * sizeof(R), hipMemcpyHostToDevice));
-    }
-    return USV_OK;
-  }
-  if (f == USV_FIELD_ASMC) {   // device [16][N], host [N][16]
-    const size_t cnt = N * kAsmcN;
-    std::vector<R> tmp(cnt);
-    double* hd = (double*)host;
-    if (to_host) {
-      HIP_TRY(hipMemcpy(tmp.data(), S.asmc, cnt * sizeof(R), hipMemcpyDeviceToHost));
-      for (size_t e = 0; e < N; ++e)
-        for (int i = 0; i < kAsmcN; ++i) hd[e * kAsmcN + i] = (double)tmp[(size_t)i * N + e];
-    } else {
-      for (size_t e = 0; e < N; ++e)
-        for (int i = 0; i < kAsmcN; ++i) tmp[(size_t)i * N + e] = (R)hd[e * kAsmcN + i];
-      HIP_TRY(hipMemcpy(S.asmc, tmp.data(), cnt * sizeof(R), hipMemcpyHostToDevice));
-    }
-    // psi_d_last between the reference's frame (host) and the heading's (device, f32)
-    if (turn_frame<R>(h)) return heading_io<R>(h, S, f, hd, to_host);
-    return USV_OK;
-  }
-  if (f == USV_FIELD_NP_RNG || f == USV_FIELD_NP_MT) {   // device SoA uint32 rows, host [N][per] int32
-    const int per = field_per_env(h, f);
-    std::vector<uint32_t> tmp(N);
-    uint32_t* hd = (uint32_t*)host;
-    for (int i = 0; i < per; ++i) {
-      uint32_t* d = (f == USV_FIELD_NP_RNG ? S.nprng : S.npmt) + (size_t)i * S.fstride;
-      if (to_host) {
-        HIP_TRY(hipMemcpy(tmp.data(), d, N * 4, hipMemcpyDeviceToHost));
-        for (size_t e = 0; e < N; ++e) hd[e * per + i] = tmp[e];
-      } else {
-        for (size_t e = 0; e < N; ++e) tmp[e] = hd[e * per + i];
-        HIP_TRY(hipMemcpy(d, tmp.data(), N * 4, hipMemcpyHostToDevice));
-      }
-    }
-    return USV_OK;
-  }
-  if (f >= USV_FIELD_V0_LAST && f <= USV_FIELD_V0_YE) {   // device SoA rows, host [N][per]
-    const int per = field_per_env(h, f), base = v0_base(f);
-    std::vector<R> tmp(N);
-    double* hd = (double*)host;
-    for (int i = 0; i < per; ++i) {
-      if (to_host) {
-        HIP_TRY(hipMemcpy(tmp.data(), S.V(base + i), N * sizeof(R), hipMemcpyDeviceToHost));
-        for (size_t e = 0; e < N; ++e) hd[e * per + i] = (double)tmp[e];
-      } else {
-        for (size_t e = 0; e < N; ++e) tmp[e] = (R)hd[e * per + i];
-        HIP_TRY(hipMemcpy(S.V(base + i), tmp.data(), N * sizeof(R), hipMemcpyHostToDevice));
-      }
-    }
-    return USV_OK;
-  }
-  return fail(USV_ERR_ARG, "unknown field");
+  const Field& fd = h->fields.row[f];
+  char* const region = (char*)h->slab + h->lay.off[fd.region];
+  const int rc = fd.is_int ? copy_field((int32_t*)region + fd.first, fd, N, (int32_t*)host, to_host)
+                           : copy_field((R*)region + fd.first, fd, N, (double*)host, to_host);
+  // psi_d_last (ASMC row 0) between the reference's frame (host) and the heading's (device, f32)
+  if (rc == USV_OK && f == USV_FIELD_ASMC && turn_frame<R>(h)) return heading_io<R>(h, S, f, (double*)host, to_host);
+  return rc;
 }
-
-size_t field_bytes(const Handle* h, int f) {
-  return (size_t)h->cfg.num_envs * field_per_env(h, f) * (kFields[f].is_int ? 4 : 8);
+// Writes complete before returning (hipMemcpy from pageable memory may return before the DMA
+// lands), so a kernel the caller launches next on any stream sees them.
+template <typename R>
+int field_io(Handle* h, State<R>& S, int f, void* host, bool to_host) {
+  HIP_TRY(hipDeviceSynchronize());
+  const int rc = field_io_impl(h, S, f, host, to_host);
+  if (rc == USV_OK && !to_host) HIP_TRY(hipDeviceSynchronize());
+  return rc;
 }
 
 template <typename R>
@@ -699,6 +598,7 @@ int usv_create(const usv_config* cfg, int32_t device, void** out) {
   Handle* h = new Handle();
   h->cfg = *cfg;
   h->device = device;
+  if (cfg->precision == USV_F64) h->st = State<double>{};   // (else the zeroed State<float> it starts as)
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
@@ -706,7 +606,7 @@ int usv_create(const usv_config* cfg, int32_t device, void** out) {
   }
   apply_variant(h, default_variant(*cfg));
   if (const int rc = queue_lds_attr(cfg->mode, h->kind); rc != USV_OK) { delete h; return rc; }
-  const int rc = cfg->precision == USV_F32 ? carve<float>(h, h->sf) : carve<double>(h, h->sd);
+  const int rc = with_state(h, [&](auto& S) { return carve(h, S); });
   if (rc != USV_OK) {
     if (h->slab) (void)hipFree(h->slab);
     delete h;
@@ -753,7 +653,7 @@ int usv_set_reset_rng(void* hp, int32_t kind) {
   Handle* h = as_handle(hp);
   if (!h) return fail(USV_ERR_ARG, "null handle");
   if (kind != USV_RESET_PHILOX && kind != USV_RESET_NUMPY_PCG64) return fail(USV_ERR_ARG, "unknown reset rng");
-  h->sf.np_reset = h->sd.np_reset = kind == USV_RESET_NUMPY_PCG64;
+  with_state(h, [&](auto& S) { S.np_reset = kind == USV_RESET_NUMPY_PCG64; });
   return USV_OK;
 }
 
@@ -762,9 +662,10 @@ int usv_seed(void* hp, uint64_t seed) {
   if (!h) return fail(USV_ERR_ARG, "null handle");
   DeviceGuard g(h->device);
   h->cfg.seed = seed;
-  h->sf.seed = seed;
-  h->sd.seed = seed;
-  int32_t* ep = h->cfg.precision == USV_F32 ? h->sf.I(I_EPISODE) : h->sd.I(I_EPISODE);
+  int32_t* ep = with_state(h, [&](auto& S) {
+    S.seed = seed;
+    return S.I(I_EPISODE);
+  });
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemset(ep, 0, (size_t)h->cfg.num_envs * 4));
   HIP_TRY(hipDeviceSynchronize());     // ordered before launches on any (non-blocking) stream
@@ -783,8 +684,7 @@ int usv_reset_ex(void* hp, const uint8_t* mask, float* obs, const usv_reset_opti
     return fail(USV_ERR_ARG, "place_obstacles_on_path needs obstacle_cap >= 29 + k (reference draws up to 29)");
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
-  return h->cfg.precision == USV_F32 ? launch_reset<float>(h, h->sf, mask, obs, kpath, info, st)
-                                     : launch_reset<double>(h, h->sd, mask, obs, kpath, info, st);
+  return with_state(h, [&](auto& S) { return launch_reset(h, S, mask, obs, kpath, info, st); });
 }
 
 int usv_reset(void* hp, const uint8_t* mask, float* obs, void* stream) {
@@ -797,9 +697,7 @@ int usv_step_ex(void* hp, const float* act, float* obs, void* rew, uint8_t* term
   if (!h || !act || !obs || !rew || !term || !trunc) return fail(USV_ERR_ARG, "null argument");
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)stream;
-  return h->cfg.precision == USV_F32
-             ? launch_step<float>(h, h->sf, act, obs, rew, term, trunc, done, fobs, info, st)
-             : launch_step<double>(h, h->sd, act, obs, rew, term, trunc, done, fobs, info, st);
+  return with_state(h, [&](auto& S) { return launch_step(h, S, act, obs, rew, term, trunc, done, fobs, info, st); });
 }
 
 int usv_step(void* hp, const float* act, float* obs, void* rew, uint8_t* term, uint8_t* trunc,
@@ -814,70 +712,54 @@ int usv_set_experiment(void* hp, const usv_experiment* x) {
   if (x && (x->n_obs < 1 || x->n_obs > h->cfg.obstacle_cap || x->n_obs > 64))
     return fail(USV_ERR_ARG, "experiment n_obs must be in [1, obstacle_cap]");
   DeviceGuard g(h->device);
-  return h->cfg.precision == USV_F32 ? set_experiment<float>(h, h->sf, x) : set_experiment<double>(h, h->sd, x);
+  return with_state(h, [&](auto& S) { return set_experiment(h, S, x); });
 }
 
 int usv_field_info(void* hp, int32_t f, int32_t* per_env, int32_t* is_int, const char** name) {
   Handle* h = as_handle(hp);
   if (!h || f < 0 || f >= USV_FIELD_COUNT) return fail(USV_ERR_ARG, "bad handle or field");
-  if (per_env) *per_env = field_per_env(h, f);
-  if (is_int) *is_int = kFields[f].is_int;
-  if (name) *name = kFields[f].name;
+  const Field& fd = h->fields.row[f];
+  if (per_env) *per_env = fd.per;
+  if (is_int) *is_int = fd.is_int;
+  if (name) *name = fd.name;
   return USV_OK;
 }
 
-int usv_get_field(void* hp, int32_t f, void* host, size_t bytes) {
+static int field_call(void* hp, int32_t f, void* host, size_t bytes, bool to_host) {
   Handle* h = as_handle(hp);
   if (!h || !host || f < 0 || f >= USV_FIELD_COUNT) return fail(USV_ERR_ARG, "bad argument");
-  if (bytes != field_bytes(h, f)) return fail(USV_ERR_ARG, "byte count mismatch");
+  if (bytes != field_bytes(h->cfg, h->fields.row[f])) return fail(USV_ERR_ARG, "byte count mismatch");
   DeviceGuard g(h->device);
-  return h->cfg.precision == USV_F32 ? field_io<float>(h, h->sf, f, host, true)
-                                     : field_io<double>(h, h->sd, f, host, true);
+  return with_state(h, [&](auto& S) { return field_io(h, S, f, host, to_host); });
 }
-
+int usv_get_field(void* hp, int32_t f, void* host, size_t bytes) { return field_call(hp, f, host, bytes, true); }
 int usv_set_field(void* hp, int32_t f, const void* host, size_t bytes) {
-  Handle* h = as_handle(hp);
-  if (!h || !host || f < 0 || f >= USV_FIELD_COUNT) return fail(USV_ERR_ARG, "bad argument");
-  if (bytes != field_bytes(h, f)) return fail(USV_ERR_ARG, "byte count mismatch");
-  DeviceGuard g(h->device);
-  return h->cfg.precision == USV_F32 ? field_io<float>(h, h->sf, f, (void*)host, false)
-                                     : field_io<double>(h, h->sd, f, (void*)host, false);
+  return field_call(hp, f, (void*)host, bytes, false);
 }
 
 size_t usv_state_bytes(void* hp) {
   Handle* h = as_handle(hp);
   if (!h) return 0;
   size_t b = 0;
-  for (int f = 0; f < USV_FIELD_COUNT; ++f) b += field_bytes(h, f);
+  for (const Field& fd : h->fields.row) b += field_bytes(h->cfg, fd);
   return b;
 }
 
-int usv_get_state(void* hp, void* host, size_t bytes) {
+// the blob: every field's host image, in table order
+static int state_call(void* hp, void* host, size_t bytes, bool to_host) {
   Handle* h = as_handle(hp);
   if (!h || !host) return fail(USV_ERR_ARG, "bad argument");
   if (bytes != usv_state_bytes(hp)) return fail(USV_ERR_ARG, "byte count mismatch");
   char* p = (char*)host;
   for (int f = 0; f < USV_FIELD_COUNT; ++f) {
-    const size_t fb = field_bytes(h, f);
-    const int rc = usv_get_field(hp, f, p, fb);
+    const size_t fb = field_bytes(h->cfg, h->fields.row[f]);
+    const int rc = field_call(hp, f, p, fb, to_host);
     if (rc != USV_OK) return rc;
     p += fb;
   }
   return USV_OK;
 }
-
-int usv_set_state(void* hp, const void* host, size_t bytes) {
-  Handle* h = as_handle(hp);
-  if (!h || !host) return fail(USV_ERR_ARG, "bad argument");
-  if (bytes != usv_state_bytes(hp)) return fail(USV_ERR_ARG, "byte count mismatch");
-  const char* p = (const char*)host;
-  for (int f = 0; f < USV_FIELD_COUNT; ++f) {
-    const size_t fb = field_bytes(h, f);
-    const int rc = usv_set_field(hp, f, p, fb);
-    if (rc != USV_OK) return rc;
-    p += fb;
-  }
-  return USV_OK;
-}
+int usv_get_state(void* hp, void* host, size_t bytes) { return state_call(hp, host, bytes, true); }
+int usv_set_state(void* hp, const void* host, size_t bytes) { return state_call(hp, (void*)host, bytes, false); }
 
 }  // extern "C"

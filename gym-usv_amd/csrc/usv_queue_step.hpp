@@ -37,7 +37,7 @@ constexpr int kQSgpr = 80, kQWPE = 8;
 // r5b-r5e): -0.27 to -0.67 us per launch at 65 536 envs (usv-simple), -0.95 us (usv-asmc-simple, whose
 // q kernel has the same phase 1).
 constexpr int kQPrioDyn = 3, kQYoungWaves = 10;
-constexpr int kQRec = 16;   // (the block shapes kQE / kQW, kQE_S / kQW_S: usv_variant.hpp)
+// (the block shapes kQE / kQW, kQE_S / kQW_S: usv_variant.hpp; the record's size kQRec: usv_layout.hpp)
 __host__ __device__ constexpr size_t q_slice_bytes() { return 256 * 8 + 64 * 4 + 2 * 1024; }
 
 // One DMA instruction (<= 64 pieces of 16 B, i.e. <= 1 KiB): pieces c >= nchunk are not copied.

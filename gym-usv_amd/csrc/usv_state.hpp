@@ -1,4 +1,4 @@
-// usv_state.hpp -- device state (State, IO, the field enums), the f32 heading frame, output stores and the
+// usv_state.hpp -- device state (State, IO; its rows and sizes: usv_layout.hpp), the f32 heading frame, output stores and the
 // observation header shared by every kernel.
 #pragma once
 
@@ -21,16 +21,11 @@ template <> struct V4<float> { typedef float T __attribute__((ext_vector_type(4)
 template <> struct V4<double> { typedef double T __attribute__((ext_vector_type(4))); };
 template <typename R> using R4 = typename V4<R>::T;
 
-enum RealField {
-  F_X, F_Y, F_PSI, F_U, F_V, F_R, F_LAST_U, F_LAST_R, F_PROGRESS,
-  F_PX0, F_PY0, F_PX1, F_PY1, F_MAX_U, F_MAX_R, F_REF_V, F_NREAL
-};
-
 // Device state.  All real SoA fields share one allocation (field i at freal + i*fstride) and
 // the int fields another, so the kernel holds two base pointers instead of twenty (kernel
 // arguments live in SGPRs; fewer of them keeps the kernel at <= 80 SGPRs = 8 blocks per CU).
-// I_TURNS (f32 usv-simple / usv-asmc-simple): whole turns of the heading, see store_heading
-enum IntField { I_NOBS, I_ELAPSED, I_EPISODE, I_SCAN, I_TURNS, I_NINT };
+// The row enums (RealField, IntField, kV0*), the sizes and the slab the pointers are carved from
+// are in usv_layout.hpp.
 template <typename R> struct State {
   R* freal;                // [F_NREAL][fstride]
   int32_t* fint;           // [I_NINT][fstride]
@@ -64,7 +59,6 @@ template <typename R> struct State {
   __host__ __device__ R* V(int i) const { return v0 + (size_t)i * fstride; }
   __host__ __device__ R* orow(int e) const { return obst + (size_t)e * 3 * ostride; }
 };
-constexpr int kV0Last = 0, kV0Aux = 9, kV0Target = 12, kV0ALast = 18, kV0Ye = 19, kV0N = 21;
 
 // Heading representation of the f32 usv-simple / usv-asmc-simple state.  The reference integrates the
 // heading without wrapping (simple_env.py:323, usv_asmc.py:234), so it grows without bound, and a float
@@ -105,10 +99,6 @@ template <typename R> __device__ __forceinline__ R heading_abs(R phi, int k) {
     return phi;
   }
 }
-// custom experiment record (usv_experiment, simple_env.py:292-300), in R: n, path start (2),
-// path angle, pose (3), pad, then x[cap], y[cap], r[cap]
-constexpr int kExpN = 0, kExpPS = 1, kExpAngle = 3, kExpPose = 4, kExpObs = 8;
-
 template <typename R> struct IO {
   const float* act;        // [N][2]
   float* obs;              // [N][143]
