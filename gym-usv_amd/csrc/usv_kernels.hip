@@ -13,6 +13,7 @@
 //   usv_queue_step.hpp    block-queue step (queue split, fused, after the ASMC chain)
 //   usv_reset_kernel.hpp  explicit reset kernel
 //   usv_legacy.hpp        usv-asmc-v0 and the legacy float64 family
+//   usv_noscan_step.hpp   scan-free step (ignore_obstacles)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -35,6 +36,7 @@
 #include "usv_queue_step.hpp"
 #include "usv_reset_kernel.hpp"
 #include "usv_legacy.hpp"
+#include "usv_noscan_step.hpp"   // (last: the kernels before it keep their place in the code object)
 
 
 // ============================================================================= host side
@@ -62,6 +64,7 @@ struct Handle {
   // step-kernel variant: StepKind, envs per block, lidar bits (usv_variant.hpp; written by apply_variant)
   int kind = 0, epb = 0, lid = 0;
   int cus = 256;                       // compute units of the device (State::qyoung)
+  bool ignore = false;                 // ignore_obstacles (simple_env.py:49): the scan-free step replaces the variant
   void* slab = nullptr;
   SlabLayout lay{};                    // the slab's regions and the public fields in them (usv_layout.hpp)
   FieldTable fields{};
@@ -279,6 +282,11 @@ int launch_step(Handle* h, State<R>& S, const float* act, float* obs, void* rew,
   return USV_OK;
 }
 
+// The scan-free step (ignore_obstacles): defined after every other launch path, so that its kernels are
+// instantiated last and the ones before them keep their place in the code object.
+template <typename R>
+int launch_noscan(Handle* h, State<R>& S, IO<R>& io, hipStream_t st);
+
 template <typename R>
 int launch_step_kernels(Handle* h, State<R>& S, const float* act, float* obs, void* rew, uint8_t* term,
                         uint8_t* trunc, uint8_t* done, float* fobs, void* info, hipStream_t st) {
@@ -294,6 +302,7 @@ int launch_step_kernels(Handle* h, State<R>& S, const float* act, float* obs, vo
     HIP_TRY(hipGetLastError());
     return USV_OK;
   }
+  if (h->ignore) return launch_noscan(h, S, io, st);        // whatever variant is installed
   const int epb = h->epb, lid = h->lid;
   const bool simple = h->cfg.mode == USV_MODE_SIMPLE;
   void* args[] = {(void*)&S, (void*)&io};
@@ -494,6 +503,37 @@ int queue_lds_attr(int mode, int kind) {
 
 Handle* as_handle(void* p) { return static_cast<Handle*>(p); }
 
+// The scan-free step (ignore_obstacles).  usv-asmc-simple f32 runs the ASMC chain in its own launch
+// first, as the block-queue default does; f64 runs it inside the step (36.4 against 40.6 us split).
+template <typename R, int MODE, bool CHAIN>
+void* pick_noscan(bool done, bool info) {
+  if (done) return info ? (void*)&noscan_step_kernel<R, MODE, CHAIN, true, true>
+                        : (void*)&noscan_step_kernel<R, MODE, CHAIN, true, false>;
+  return info ? (void*)&noscan_step_kernel<R, MODE, CHAIN, false, true>
+              : (void*)&noscan_step_kernel<R, MODE, CHAIN, false, false>;
+}
+template <typename R>
+int launch_noscan(Handle* h, State<R>& S, IO<R>& io, hipStream_t st) {
+  // (-DUSV_NOSCAN_F64_SPLIT builds the f64 library with the chain split off too, for the A/B in DESIGN.md)
+#ifdef USV_NOSCAN_F64_SPLIT
+  constexpr bool kSplit = true;
+#else
+  constexpr bool kSplit = std::is_same<R, float>::value;
+#endif
+  const bool done = io.done != nullptr, info = io.info != nullptr;
+  const dim3 grid((S.N + kBlock - 1) / kBlock), block(kBlock);
+  void* args[] = {(void*)&S, (void*)&io};
+  void* fn;
+  if (h->cfg.mode == USV_MODE_SIMPLE) {
+    fn = pick_noscan<R, USV_MODE_SIMPLE, true>(done, info);
+  } else {
+    if constexpr (kSplit) HIP_TRY(hipLaunchKernel((void*)&asmc_chain_kernel<R>, grid, block, args, 0, st));
+    fn = pick_noscan<R, USV_MODE_ASMC_SIMPLE, !kSplit>(done, info);
+  }
+  HIP_TRY(hipLaunchKernel(fn, grid, block, args, 0, st));
+  return USV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -588,9 +628,12 @@ int usv_create(const usv_config* cfg, int32_t device, void** out) {
     return fail(USV_ERR_ARG, "unknown autoreset mode");
   if (cfg->lidar_algo != USV_LIDAR_BRUTE && cfg->lidar_algo != USV_LIDAR_WINDOW)
     return fail(USV_ERR_ARG, "unknown lidar algorithm");
-  if ((cfg->flags & ~USV_FLAG_PERTURB) != 0 || cfg->reserved != 0) return fail(USV_ERR_ARG, "unknown flags");
+  if ((cfg->flags & ~(USV_FLAG_PERTURB | USV_FLAG_IGNORE_OBSTACLES)) != 0 || cfg->reserved != 0)
+    return fail(USV_ERR_ARG, "unknown flags");
   if ((cfg->flags & USV_FLAG_PERTURB) && cfg->mode != USV_MODE_ASMC_SIMPLE)
     return fail(USV_ERR_ARG, "USV_FLAG_PERTURB applies to usv-asmc-simple only");
+  if ((cfg->flags & USV_FLAG_IGNORE_OBSTACLES) && is_legacy(cfg->mode))
+    return fail(USV_ERR_ARG, "USV_FLAG_IGNORE_OBSTACLES applies to usv-simple / usv-asmc-simple only");
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(USV_ERR_ARG, "bad device index");
@@ -598,6 +641,7 @@ int usv_create(const usv_config* cfg, int32_t device, void** out) {
   Handle* h = new Handle();
   h->cfg = *cfg;
   h->device = device;
+  h->ignore = (cfg->flags & USV_FLAG_IGNORE_OBSTACLES) != 0;
   if (cfg->precision == USV_F64) h->st = State<double>{};   // (else the zeroed State<float> it starts as)
   {
     int cus = 0;
@@ -627,6 +671,23 @@ int usv_set_kernel_variant(void* hp, int32_t kind, int32_t epb, int32_t lid) {
   if (const int rc = queue_lds_attr(h->cfg.mode, kind); rc != USV_OK) return rc;
   apply_variant(h, c.v);
   return USV_OK;
+}
+
+int usv_set_ignore_obstacles(void* hp, int32_t on) {
+  Handle* h = as_handle(hp);
+  if (!h) return fail(USV_ERR_ARG, "null handle");
+  if (is_legacy(h->cfg.mode))
+    return fail(USV_ERR_ARG, "ignore_obstacles applies to usv-simple / usv-asmc-simple only");
+  DeviceGuard g(h->device);
+  HIP_TRY(hipDeviceSynchronize());                 // launches in flight keep the step they took
+  h->ignore = on != 0;                             // (the installed variant stays, for the toggle back)
+  return USV_OK;
+}
+
+int usv_get_ignore_obstacles(void* hp) {
+  Handle* h = as_handle(hp);
+  if (!h) return fail(USV_ERR_ARG, "null handle");
+  return h->ignore ? 1 : 0;
 }
 
 void usv_destroy(void* hp) {

@@ -11,6 +11,7 @@ namespace usv {
 // Explicit (host-requested) reset of masked envs.  Reset obs = new header + the stale
 // sensor_data: the scan at the last stepped pose (recomputed when that pose is still the
 // current one, else the stored one; zeros for a never-stepped env), simple_env.py:302.
+// scan_valid == 2: the last step was a scan-free one (ignore_obstacles), its scan is all max range.
 template <typename R, int MODE>
 __global__ __launch_bounds__(kBlock) void reset_kernel(State<R> S, IO<R> io) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -33,7 +34,13 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(State<R> S, IO<R> io) {
     if (io.mask && !io.mask[e]) continue;
     R rd0, rd1;
     R* last = S.sensor_last + (size_t)e * kSensors;
-    if (S.I(I_SCAN)[e]) {
+    const int valid = uniform(S.I(I_SCAN)[e]);
+    if (valid == 2) {
+      // the last step ignored the obstacles (noscan_step_kernel): 128 readings of 100 (:222-224)
+      rd0 = rd1 = R(kSensorMax);
+      last[l] = rd0;
+      last[64 + l] = rd1;
+    } else if (valid) {
       R sp, cp;
       heading_sincos(S.F(F_PSI)[e], &sp, &cp);
       const int n = uniform(S.I(I_NOBS)[e]);

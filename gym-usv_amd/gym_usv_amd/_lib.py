@@ -22,6 +22,7 @@ LIDAR_BRUTE, LIDAR_WINDOW = 0, 1
 RESET_PHILOX, RESET_NUMPY_PCG64 = 0, 1
 OBS_DIM, SENSOR_COUNT, ACT_DIM, ASMC_STATE = 143, 128, 2, 16
 FLAG_PERTURB = 1
+FLAG_IGNORE_OBSTACLES = 2
 # usv_info_key order (include/usv_hip.h): reference info keys (simple_env.py:102-115, 189-199) -> column
 INFO_KEYS = ("x", "y", "psi", "u", "v", "r", "path_x0", "path_y0", "path_x1", "path_y1", "action0",
              "action1", "ye", "angle_to_target", "ye_reward", "angle_to_target_reward",
@@ -82,6 +83,8 @@ SIGNATURES = [
     ("usv_get_state", ctypes.c_int, [_vp, _vp, _sz]),
     ("usv_set_state", ctypes.c_int, [_vp, _vp, _sz]),
     ("usv_set_kernel_variant", ctypes.c_int, [_vp, _i32, _i32, _i32]),
+    ("usv_set_ignore_obstacles", ctypes.c_int, [_vp, _i32]),
+    ("usv_get_ignore_obstacles", ctypes.c_int, [_vp]),
     ("usv_config_size", _sz, []),
     ("usv_asmc_compute", ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
 ]

@@ -24,7 +24,8 @@ class _SingleEnv:
     metadata = {"render_modes": [], "render_fps": 30}
 
     def __init__(self, render_mode=None, options=None, device=0, precision="f32",
-                 max_episode_steps=0, seed=None, reset_rng="numpy", obstacle_cap=32, perturb=False):
+                 max_episode_steps=0, seed=None, reset_rng="numpy", obstacle_cap=32, perturb=False,
+                 ignore_obstacles=False):
         if render_mode not in (None, "rgb_array"):
             raise NotImplementedError("render_mode 'human' (a pygame window) is out of scope; use 'rgb_array'")
         self.render_mode = render_mode
@@ -33,10 +34,19 @@ class _SingleEnv:
                                   autoreset=False, max_episode_steps=max_episode_steps,
                                   seed=0 if seed is None else seed, reset_rng=reset_rng,
                                   obstacle_cap=obstacle_cap, options=self.options, info=True,
-                                  perturb=perturb)
+                                  perturb=perturb, ignore_obstacles=ignore_obstacles)
         self.observation_space = self._venv.single_observation_space
         self.action_space = self._venv.single_action_space
         self._seeded = False
+
+    @property
+    def ignore_obstacles(self):
+        """The reference's attribute (simple_env.py:49): ``env.ignore_obstacles = True`` after make()."""
+        return self._venv.ignore_obstacles
+
+    @ignore_obstacles.setter
+    def ignore_obstacles(self, on):
+        self._venv.ignore_obstacles = on
 
     def reset(self, seed=None, options=None):
         if seed is None and not self._seeded:

@@ -172,13 +172,15 @@ class UsvVectorEnv:
     def __init__(self, env_id="usv-simple", num_envs=4096, device=0, seed=0, precision="f32",
                  autoreset=True, max_episode_steps=None, obstacle_cap=32, lidar="window",
                  env_id_offset=0, reset_rng="philox", options=None, info=False, perturb=False,
-                 copy=True, kernel_variant=None, lib_path=None):
+                 copy=True, kernel_variant=None, lib_path=None, ignore_obstacles=False):
         """``options`` are UsvSimpleEnv's constructor options (simple_env.py:10): only
         ``run_custom_experiment`` / ``experiment`` (:292-300) exist there.  ``info=True`` returns the
         reference's per-step info keys (simple_env.py:102-115, 189-199) as device tensors.
         ``perturb=True`` runs usv-asmc-simple's UsvAsmc.compute with do_perturb (usv_asmc.py:184-199).
         ``kernel_variant="epb,lid,kind"`` selects a step-kernel variant (usv_set_kernel_variant; all
-        variants give bit-identical outputs, the GPU tests compare them); None = the tuned default."""
+        variants give bit-identical outputs, the GPU tests compare them); None = the tuned default.
+        ``ignore_obstacles=True`` starts with UsvSimpleEnv.ignore_obstacles set (simple_env.py:49; see
+        the ``ignore_obstacles`` property); usv-simple / usv-asmc-simple only."""
         if env_id not in ENV_SPECS:
             raise ValueError(f"unknown env id {env_id!r}; known: {sorted(ENV_SPECS)}")
         if not torch.cuda.is_available():
@@ -196,7 +198,7 @@ class UsvVectorEnv:
         cfg.lidar_algo = {"brute": _lib.LIDAR_BRUTE, "window": _lib.LIDAR_WINDOW}[lidar]
         cfg.seed = int(seed)
         cfg.env_id_offset = int(env_id_offset)
-        cfg.flags = _lib.FLAG_PERTURB if perturb else 0
+        cfg.flags = (_lib.FLAG_PERTURB if perturb else 0) | (_lib.FLAG_IGNORE_OBSTACLES if ignore_obstacles else 0)
         self.cfg = cfg
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
@@ -251,6 +253,23 @@ class UsvVectorEnv:
 
     def _check(self, rc):
         return _lib.check(rc, self.lib)
+
+    @property
+    def ignore_obstacles(self):
+        """UsvSimpleEnv.ignore_obstacles (simple_env.py:49), read/write like the reference's attribute.
+        While True every step is scan-free: sensors 1.0 (:222-224), no collision penalty (:155), no
+        termination on an obstacle (:334); resets still draw the obstacles, and a reset obs carries the
+        stale scan of the last step taken.  Setting it waits for the launches in flight."""
+        return bool(self._check_nonneg(self.lib.usv_get_ignore_obstacles(self._h)))
+
+    @ignore_obstacles.setter
+    def ignore_obstacles(self, on):
+        self._check(self.lib.usv_set_ignore_obstacles(self._h, 1 if on else 0))
+
+    def _check_nonneg(self, rc):
+        if rc < 0:
+            self._check(rc)
+        return rc
 
     def set_experiment(self, exp):
         """Install a custom experiment (simple_env.py:292-300) for every env: each reset keeps its

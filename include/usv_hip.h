@@ -18,6 +18,8 @@
  *   usv_reset_ex    <- UsvSimpleEnv.reset(options={'place_obstacles_on_path': k}) (:276-288) and
  *                      its info dict _get_info(-1, zeros(3)) (simple_env.py:102-115, :305)
  *   usv_set_experiment <- UsvSimpleEnv(options={'run_custom_experiment': ..}) (:10, :292-300)
+ *   usv_set_ignore_obstacles <- the attribute UsvSimpleEnv.ignore_obstacles (simple_env.py:49,
+ *                      read at :155, :222-224, :334)
  *   usv_step_ex     <- the step's info dict (simple_env.py:102-115, 189-199, 343-344)
  *   usv_step        <- UsvSimpleEnv.step (simple_env.py:310-346),
  *                      UsvSimpleASMCEnv.step (simple_env_asmc.py:18-27) -> UsvAsmc.compute
@@ -113,7 +115,11 @@ typedef enum usv_flags {
   /* usv-asmc-simple: UsvAsmc.compute(..., do_perturb=True) (gym_usv/control/usv_asmc.py:184-199):
      a sinusoidal force is added to the thrust every substep; the controller's perturb_step is
      20 * elapsed + substep (a fresh UsvAsmc per episode, 2 x 10 substeps per env step) */
-  USV_FLAG_PERTURB = 1
+  USV_FLAG_PERTURB = 1,
+  /* usv-simple / usv-asmc-simple: UsvSimpleEnv.ignore_obstacles (gym_usv/envs/simple_env.py:49) set
+     from the start; usv_set_ignore_obstacles toggles it later.  USV_ERR_ARG for the legacy *-v0 ids,
+     which have no obstacles. */
+  USV_FLAG_IGNORE_OBSTACLES = 2
 } usv_flags;
 
 /* Per-step info (opt-in, usv_step_ex / usv_reset_ex): one row of USV_INFO_DIM values per env, in the
@@ -170,7 +176,8 @@ typedef enum usv_field {
   USV_FIELD_N_OBS,          /* int: obstacle_n (:44)                                    */
   USV_FIELD_ELAPSED,        /* int: TimeLimit elapsed steps                              */
   USV_FIELD_EPISODE,        /* int: episode counter (Philox counter word)                */
-  USV_FIELD_SCAN_VALID,     /* int: 1 if the current pose's scan is the stale sensor_data */
+  USV_FIELD_SCAN_VALID,     /* int: 1 if the current pose's scan is the stale sensor_data; 2 if the
+                               stale sensor_data is all max range (last step ignored the obstacles) */
   USV_FIELD_OBS_X, USV_FIELD_OBS_Y, USV_FIELD_OBS_R,    /* [cap] obstacles (:45-46)    */
   USV_FIELD_SENSOR_LAST,    /* [128] stale scan for reset obs (sensor_data, :47)          */
   USV_FIELD_ASMC,           /* [16] UsvAsmc state (usv-asmc-simple only)                  */
@@ -275,6 +282,25 @@ int usv_asmc_compute(int32_t precision, int32_t n, const void* act_dev, void* po
  *        on from 196 608 envs, where the rows go to DRAM)
  * Waits for in-flight launches first.  USV_ERR_ARG if the handle's config cannot run it. */
 int usv_set_kernel_variant(void* handle, int32_t kind, int32_t epb, int32_t lid);
+
+/* UsvSimpleEnv.ignore_obstacles (gym_usv/envs/simple_env.py:49; UsvSimpleASMCEnv inherits it), an
+ * attribute the reference's users set after make().  While it is on, for usv-simple / usv-asmc-simple:
+ *   - every lidar reading is the maximum range (:222-224): obs[15:143] = 100 / 100 = 1.0f exactly;
+ *   - the reward has no -20 collision term (:155): rew_dev is the sum of the other terms;
+ *   - no env terminates on an obstacle (:334): term_dev is 0, done_dev equals trunc_dev;
+ *   - kinematics, the ASMC chain, closest point, obs header, truncation, TimeLimit and the info rows are
+ *     those of the scanning step, bit for bit (the same device code);
+ *   - resets draw as always, obstacles included (the reference draws them, and a later toggle-off finds
+ *     them); a reset obs carries the stale sensor_data (:302, :47), which follows the mode of the last
+ *     step taken: 1.0 after an ignoring step, the last real scan after a scanning one, zeros for a
+ *     never-stepped env.
+ * usv_step / usv_step_ex then launch a scan-free kernel instead of the installed step variant, which is
+ * kept and used again after toggle-off.  Such a step leaves USV_FIELD_SCAN_VALID = 2: "the stale scan is
+ * 128 readings of 100"; a reset turns that into USV_FIELD_SENSOR_LAST = 100 and scan_valid = 0.
+ * The setter waits for in-flight launches first; USV_ERR_ARG for the legacy *-v0 ids.  The getter
+ * returns 0 / 1, or a negative usv_status.  USV_FLAG_IGNORE_OBSTACLES sets the initial value. */
+int usv_set_ignore_obstacles(void* handle, int32_t on);
+int usv_get_ignore_obstacles(void* handle);
 
 /* Field metadata: values per env, 1 if int32, name. */
 int usv_field_info(void* handle, int32_t field, int32_t* per_env, int32_t* is_int,
