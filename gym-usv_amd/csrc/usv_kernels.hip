@@ -14,6 +14,8 @@
 //   usv_reset_kernel.hpp  explicit reset kernel
 //   usv_legacy.hpp        usv-asmc-v0 and the legacy float64 family
 //   usv_noscan_step.hpp   scan-free step (ignore_obstacles)
+//   usv_wrap_layout.hpp   the fused wrappers' frame ring: slots, stride, window (host C++, no HIP)
+//   usv_wrap.hpp          frame stack + episode statistics behind the step (usv_wrap_step / _reset)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -36,7 +38,8 @@
 #include "usv_queue_step.hpp"
 #include "usv_reset_kernel.hpp"
 #include "usv_legacy.hpp"
-#include "usv_noscan_step.hpp"   // (last: the kernels before it keep their place in the code object)
+#include "usv_noscan_step.hpp"   // (after the others: the kernels before it keep their place in the code object)
+#include "usv_wrap.hpp"
 
 
 // ============================================================================= host side
@@ -822,5 +825,104 @@ static int state_call(void* hp, void* host, size_t bytes, bool to_host) {
 }
 int usv_get_state(void* hp, void* host, size_t bytes) { return state_call(hp, host, bytes, true); }
 int usv_set_state(void* hp, const void* host, size_t bytes) { return state_call(hp, (void*)host, bytes, false); }
+
+// ---- fused wrappers (usv_wrap.hpp): handle-free, stream-ordered, like usv_asmc_compute
+size_t usv_wrap_ring_stride(int32_t obs_dim, int32_t n_stack) {
+  return obs_dim > 0 && n_stack >= 1 ? wrap_ring_stride(obs_dim, n_stack) : 0;
+}
+
+size_t usv_wrap_window_offset(int32_t obs_dim, int32_t n_stack, int64_t j) {
+  return obs_dim > 0 && n_stack >= 1 && j >= 0 ? wrap_window_offset(obs_dim, n_stack, j) : 0;
+}
+
+// The shape checks (before any HIP call), then the buffers' device; fills the kernel's arguments.
+static int wrap_args(const usv_wrap* w, int64_t j, std::initializer_list<const void*> more, WrapArgs& a, int& dev) {
+  if (!w) return fail(USV_ERR_ARG, "null usv_wrap");
+  if (w->n <= 0 || w->obs_dim <= 0 || w->n_stack < 1)
+    return fail(USV_ERR_ARG, "usv_wrap: n and obs_dim must be > 0 and n_stack >= 1");
+  if (!w->ring) return fail(USV_ERR_ARG, "usv_wrap: null ring");
+  if (w->reward_bytes != 4 && w->reward_bytes != 8) return fail(USV_ERR_ARG, "usv_wrap: reward_bytes must be 4 or 8");
+  if (j < 0) return fail(USV_ERR_ARG, "usv_wrap: the step counter j must be >= 0");
+  if ((w->flags & ~USV_WRAP_CLEAR_KEEPS_SIGN) != 0 || w->reserved != 0)
+    return fail(USV_ERR_ARG, "usv_wrap: unknown flags");
+  if (!w->ep_ret || !w->ep_len) return fail(USV_ERR_ARG, "usv_wrap: null ep_ret / ep_len");
+  if (!!w->cum_ret != !!w->cum_len || !!w->cum_ret != !!w->cum_eps)
+    return fail(USV_ERR_ARG, "usv_wrap: cum_ret, cum_len and cum_eps are given together or not at all");
+  for (const void* p : more)
+    if (!p) return fail(USV_ERR_ARG, "usv_wrap: null argument");
+  auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
+  if (misaligned(w->ring, 4) || misaligned(w->ep_len, 4) || misaligned(w->ep_ret, 8) || misaligned(w->episode, 8) ||
+      misaligned(w->cum_ret, 8) || misaligned(w->cum_len, 8) || misaligned(w->cum_eps, 8))
+    return fail(USV_ERR_ARG, "usv_wrap: a buffer is not aligned to its element size");
+  auto device_of = [](const void* p) {
+    hipPointerAttribute_t pa{};
+    return hipPointerGetAttributes(&pa, p) == hipSuccess ? pa.device : -1;
+  };
+  dev = device_of(w->ring);
+  if (dev < 0) { (void)hipGetLastError(); return fail(USV_ERR_ARG, "usv_wrap: ring is not a device pointer"); }
+  bool same = true;
+  for (const void* p : {(const void*)w->ep_ret, (const void*)w->ep_len, (const void*)w->episode,
+                        (const void*)w->cum_ret, (const void*)w->cum_len, (const void*)w->cum_eps})
+    same = same && (!p || device_of(p) == dev);
+  for (const void* p : more) same = same && device_of(p) == dev;
+  if (!same) {
+    (void)hipGetLastError();
+    return fail(USV_ERR_ARG, "usv_wrap: a buffer is not a device pointer on the ring's device");
+  }
+  const int k = w->n_stack;
+  a = WrapArgs{w->n, w->obs_dim, k, w->reward_bytes, wrap_slot(j, k), wrap_mirror_slot(j, k),
+               wrap_terminal_slot(j, k), (w->flags & USV_WRAP_CLEAR_KEEPS_SIGN) != 0, wrap_ring_stride(w->obs_dim, k), w->ring,
+               w->ep_ret, w->ep_len, w->episode, w->cum_ret, (long long*)w->cum_len, (long long*)w->cum_eps};
+  return USV_OK;
+}
+
+int usv_wrap_reset(const usv_wrap* w, int64_t j, const uint8_t* mask, const float* obs, void* stream) {
+  WrapArgs a;
+  int dev;
+  if (int rc = wrap_args(w, j, {obs}, a, dev)) return rc;
+  if (mask) {
+    hipPointerAttribute_t pa{};
+    if (hipPointerGetAttributes(&pa, mask) != hipSuccess || pa.device != dev) {
+      (void)hipGetLastError();
+      return fail(USV_ERR_ARG, "usv_wrap: mask is not a device pointer on the ring's device");
+    }
+  }
+  if ((reinterpret_cast<uintptr_t>(obs) & 3) != 0) return fail(USV_ERR_ARG, "usv_wrap: obs is not 4-B aligned");
+  DeviceGuard g(dev);
+  const int per_block = kWaves * kWrapEnvs;
+  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
+  if (mask)
+    hipLaunchKernelGGL(wrap_reset_kernel<true>, grid, block, 0, (hipStream_t)stream, a, mask, obs);
+  else
+    hipLaunchKernelGGL(wrap_reset_kernel<false>, grid, block, 0, (hipStream_t)stream, a, mask, obs);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_wrap_step(const usv_wrap* w, int64_t j, const float* obs, const void* rew, const uint8_t* done,
+                  const float* final_obs, float* final_stack, void* stream) {
+  WrapArgs a;
+  int dev;
+  if (final_stack && !final_obs && w && w->n > 0 && w->obs_dim > 0 && w->n_stack >= 1 && w->ring)
+    return fail(USV_ERR_ARG, "usv_wrap_step: final_stack needs final_obs");
+  int rc = final_stack ? wrap_args(w, j, {obs, rew, done, final_obs, final_stack}, a, dev)
+                       : wrap_args(w, j, {obs, rew, done}, a, dev);
+  if (rc) return rc;
+  auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
+  if (misaligned(obs, 4) || misaligned(rew, a.reward_bytes) || (final_stack && (misaligned(final_obs, 4) || misaligned(final_stack, 4))))
+    return fail(USV_ERR_ARG, "usv_wrap_step: a buffer is not aligned to its element size");
+  DeviceGuard g(dev);
+  const int per_block = kWaves * kWrapEnvs;
+  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
+  const float* const fobs = final_stack ? final_obs : nullptr;
+  if (a.reward_bytes == 8)
+    hipLaunchKernelGGL(wrap_step_kernel<double>, grid, block, 0, (hipStream_t)stream, a, obs, (const double*)rew,
+                       done, fobs, final_stack);
+  else
+    hipLaunchKernelGGL(wrap_step_kernel<float>, grid, block, 0, (hipStream_t)stream, a, obs, (const float*)rew,
+                       done, fobs, final_stack);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
 
 }  // extern "C"

@@ -56,8 +56,21 @@ class UsvExperiment(ctypes.Structure):
                 ("angle", ctypes.c_double), ("position", ctypes.c_double * 3)]
 
 
+WRAP_CLEAR_KEEPS_SIGN = 1
+
+
+class UsvWrap(ctypes.Structure):
+    """usv_wrap: the caller-owned device buffers of the fused wrappers (usv_wrap_step / usv_wrap_reset)."""
+    _fields_ = [("n", ctypes.c_int32), ("obs_dim", ctypes.c_int32), ("n_stack", ctypes.c_int32),
+                ("reward_bytes", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("ring", ctypes.c_void_p), ("ep_ret", ctypes.c_void_p),
+                ("ep_len", ctypes.c_void_p), ("episode", ctypes.c_void_p), ("cum_ret", ctypes.c_void_p),
+                ("cum_len", ctypes.c_void_p), ("cum_eps", ctypes.c_void_p)]
+
+
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
+_i64 = ctypes.c_int64
 SIGNATURES = [
     ("usv_abi_version", ctypes.c_int, []),
     ("usv_last_error", ctypes.c_char_p, []),
@@ -87,6 +100,10 @@ SIGNATURES = [
     ("usv_get_ignore_obstacles", ctypes.c_int, [_vp]),
     ("usv_config_size", _sz, []),
     ("usv_asmc_compute", ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    ("usv_wrap_ring_stride", _sz, [_i32, _i32]),
+    ("usv_wrap_window_offset", _sz, [_i32, _i32, _i64]),
+    ("usv_wrap_reset", ctypes.c_int, [ctypes.POINTER(UsvWrap), _i64, _vp, _vp, _vp]),
+    ("usv_wrap_step", ctypes.c_int, [ctypes.POINTER(UsvWrap), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _LIBS = {}

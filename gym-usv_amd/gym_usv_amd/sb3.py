@@ -100,10 +100,15 @@ class Sb3VecEnv:
 
     ``venv`` may be passed instead of ``env_id`` (anything with the ``UsvVectorEnv`` surface:
     ``num_envs``, ``obs_dim``, ``act_dim``, ``single_*_space``, ``reset(seed=)``, ``step()`` with
-    same-step autoreset and ``info["final_obs"]``)."""
+    same-step autoreset and ``info["final_obs"]``).
+
+    ``fused=True`` computes the frame stack and the Monitor statistics with one HIP launch per step
+    (``gym_usv_amd.wrappers.DeviceWrappers``: a mirrored frame ring, nothing shifted) instead of the
+    torch ops of the default path; the returned arrays and infos are the same, bit for bit.  It needs the HIP library
+    and a GPU ``venv``: ``UsvLibError`` otherwise (no CPU fallback)."""
 
     def __init__(self, env_id="usv-simple", num_envs=4096, frame_stack=0, seed=0, venv=None,
-                 fresh_infos=False, **kw):
+                 fresh_infos=False, fused=False, **kw):
         if venv is None:
             from .vector_env import UsvVectorEnv
             # each step is consumed (copied to the host) before the next: the persistent buffers do
@@ -113,7 +118,18 @@ class Sb3VecEnv:
         self.num_envs = venv.num_envs
         self.render_mode = "rgb_array"               # VecVideoRecorder: env 0 (render.py)
         d = venv.obs_dim
-        self._stack = DeviceFrameStack(self.num_envs, d, frame_stack, venv.device) if frame_stack else None
+        self._stack = DeviceFrameStack(self.num_envs, d, frame_stack, venv.device) if frame_stack and not fused else None
+        # fused=True: the frame stack and the episode statistics are one HIP launch behind the step
+        # (wrappers.DeviceWrappers) instead of the torch ops below; same arrays and infos
+        self._wrap = None
+        if fused:
+            from .wrappers import DeviceWrappers
+            rdt = venv.reward.dtype if hasattr(venv, "reward") else torch.float32
+            # clear_keeps_sign: a done env's stack cleared as _step_wait's mask multiply clears it (x * 0),
+            # so that both modes return the same bits, the sign of a cleared frame's zeros included
+            self._wrap = DeviceWrappers(self.num_envs, d, frame_stack or 1, venv.device, rdt,
+                                        clear_keeps_sign=True)
+        self._frame_stack = frame_stack
         obs_space = venv.single_observation_space
         if frame_stack:
             obs_space = Box(np.tile(obs_space.low, frame_stack), np.tile(obs_space.high, frame_stack),
@@ -151,6 +167,9 @@ class Sb3VecEnv:
         self._ep_len.zero_()
         if self._stack is not None:
             obs = self._stack.reset(obs)
+        if self._wrap is not None:
+            stacked = self._wrap.reset(obs)
+            obs = stacked if self._frame_stack else obs
         return obs.cpu().numpy()
 
     def step_async(self, actions):
@@ -163,6 +182,8 @@ class Sb3VecEnv:
         return self._step_wait()
 
     def _step_wait(self):
+        if self._wrap is not None:
+            return self._step_wait_fused()
         venv, n, dev = self.venv, self.num_envs, self.venv.device
         np.copyto(self._act_host.numpy(), np.asarray(self._actions, dtype=np.float32).reshape(n, -1))
         self._act_dev.copy_(self._act_host, non_blocking=self._cuda)
@@ -234,6 +255,63 @@ class Sb3VecEnv:
         self._filled = idx
         if self._cuda:
             obs_done.synchronize()
+        return h["obs"].numpy(), h["rew"].numpy(), done_np, list(infos)
+
+    def _step_wait_fused(self):
+        """_step_wait with the stack and the statistics from DeviceWrappers.step; the host side (copies,
+        infos) is the same."""
+        venv, n, dev = self.venv, self.num_envs, self.venv.device
+        np.copyto(self._act_host.numpy(), np.asarray(self._actions, dtype=np.float32).reshape(n, -1))
+        self._act_dev.copy_(self._act_host, non_blocking=True)
+        obs, rew, term, trunc, info = venv.step(self._act_dev)
+        done = info["_final_obs"]
+        stacked, fstack, episode = self._wrap.step(obs, rew, done, info["final_obs"])
+        if self._frame_stack:
+            obs = stacked                               # a window of the ring, valid until the next step
+        h = self._host[self._hb]
+        self._hb ^= 1
+        main = torch.cuda.current_stream(dev)
+        ready = torch.cuda.Event()
+        ready.record(main)
+        cs = self._copy_stream
+        cs.wait_event(ready)
+        with torch.cuda.stream(cs):
+            h["obs"].copy_(obs, non_blocking=True)
+            obs_done = torch.cuda.Event()
+            obs_done.record(cs)
+        obs.record_stream(cs)
+        self._rew32.copy_(rew)
+        h["rew"].copy_(self._rew32, non_blocking=True)
+        h["done"].copy_(done, non_blocking=True)
+        small = torch.cuda.Event()
+        small.record(main)
+        small.synchronize()
+        if self._fresh_infos:
+            infos = self._infos = [{} for _ in range(n)]
+        else:
+            infos = self._infos
+            for i in self._filled:
+                infos[i] = {}
+            if any(infos):
+                for i, d in enumerate(infos):
+                    if d:
+                        infos[i] = {}
+        done_np = h["done"].numpy()
+        idx = np.flatnonzero(done_np)
+        if idx.size:
+            ti = torch.from_numpy(idx).to(dev)
+            rows = fstack[ti]
+            w = rows.shape[1]
+            # one device->host copy: terminal rows, TimeLimit.truncated, episode return and length
+            pack = torch.cat((rows.to(torch.float64), (trunc & ~term)[ti, None].to(torch.float64),
+                              episode[ti]), dim=1).cpu().numpy()
+            t = round(time.time() - self._t0, 6)
+            term_obs = pack[:, :w].astype(np.float32)
+            for j, i in enumerate(idx):
+                infos[i] = {"terminal_observation": term_obs[j], "TimeLimit.truncated": bool(pack[j, w]),
+                            "episode": {"r": round(float(pack[j, w + 1]), 6), "l": int(pack[j, w + 2]), "t": t}}
+        self._filled = idx
+        obs_done.synchronize()                          # before the next step writes into the ring
         return h["obs"].numpy(), h["rew"].numpy(), done_np, list(infos)
 
     def step(self, actions):

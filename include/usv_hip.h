@@ -31,6 +31,9 @@
  *                      UsvPidEnv.step (usv_pid_env.py:89-233, :329-338)
  *   usv_asmc_compute <- UsvAsmc.compute (gym_usv/control/usv_asmc.py:53-244), the controller
  *                      on its own, as the reference's tests drive it (tests/test_usv_asmc.py:8-37)
+ *   usv_wrap_step / usv_wrap_reset <- VecFrameStack(env, 5) (train_test/sb3_train_vec.py:70; SB3
+ *                      StackedObservations), gym.wrappers.RecordEpisodeStatistics (:43) and the
+ *                      Monitor make_vec_env puts on each env (:67)
  *   usv_get_field / usv_set_field / usv_get_state / usv_set_state
  *                   <- the env attributes (position, velocity, obstacle_positions, ...);
  *                      used for checkpointing and for parity state injection
@@ -266,6 +269,62 @@ int usv_step_ex(void* handle, const float* act_dev, float* obs_dev, void* rew_de
 int usv_asmc_compute(int32_t precision, int32_t n, const void* act_dev, void* pos_dev, void* vel_dev,
                      void* state_dev, int32_t* perturb_step_dev, int32_t do_perturb, int32_t calls,
                      void* stream);
+
+/* Fused training wrappers: the two wrappers the reference's training setup puts on every env, for all
+ * envs in one launch behind usv_step on the same stream, with no host sync:
+ *   usv_wrap_step  <- VecFrameStack(env, 5) (train_test/sb3_train_vec.py:70), i.e. SB3
+ *                     StackedObservations.update (channels-last: roll by one obs, a done env's stack
+ *                     zeroed, the new obs pushed; terminal_observation = the old stack rolled, with the
+ *                     final obs as its last frame), and RecordEpisodeStatistics (:43) / SB3 Monitor
+ *                     (make_vec_env wraps every env in one, :67): episode return and length, emitted
+ *                     and restarted when the env is done
+ *   usv_wrap_reset <- StackedObservations.reset (zeros, the reset obs last) and Monitor.reset
+ * Handle-free and stream-ordered like usv_asmc_compute (ABI v5 addition); launched on the device that
+ * holds `ring`.  The stack is a mirrored ring, never shifted: per env one row of
+ * usv_wrap_ring_stride(obs_dim, n_stack) floats (2 n_stack - 1 slots of obs_dim floats, rounded up to 4
+ * floats).  The caller counts steps: j is the index of the frame being written, the same for every env,
+ * j >= 0, and successive steps pass j, j + 1, ...  After the call with j, the stacked observation of env
+ * e is the n_stack * obs_dim floats at ring + e * stride + usv_wrap_window_offset(obs_dim, n_stack, j),
+ * oldest frame first: for all envs one [n][n_stack * obs_dim] view with row stride `stride`, valid until
+ * the next call.  n_stack = 1 keeps the statistics only (the ring is then a copy of obs).
+ *
+ * usv_wrap_step, per env, in this order:
+ *   ep_ret += reward (f64; the reward read as f32 or f64 by reward_bytes), ep_len += 1;
+ *   if done_dev[e]: final_stack_dev[e] = (frames j-n_stack+1 .. j-1, final_obs_dev[e]) unless NULL;
+ *     episode[e] = (ep_ret, ep_len); cum_ret[e] += ep_ret, cum_len[e] += ep_len, cum_eps[e] += 1;
+ *     ep_ret = ep_len = 0; the frames before j become zero;
+ *   frame j = obs_dev[e].
+ * Rows of final_stack_dev and episode of envs that are not done are left untouched.  No atomics: the
+ * interval totals are cum_*.sum(), taken by the caller when it reports.
+ * "Become zero": +0.0 is stored, as StackedObservations' `stacked_obs[i] = 0` does.  With
+ * USV_WRAP_CLEAR_KEEPS_SIGN in `flags` the step multiplies those frames by zero instead, which keeps
+ * each value's sign (-0.0 where the frame was negative): what a stack cleared by a mask multiply
+ * holds, as the default path of gym_usv_amd.sb3.Sb3VecEnv clears it, so that the fused adapter equals
+ * that path bit for bit.  The two differ only in the sign of zeros, which a later terminal stack shows.
+ * usv_wrap_reset, for envs whose mask byte is non-zero (all if mask_dev == NULL): the frames before j
+ * become zero, frame j = obs_dev[e], ep_ret = ep_len = 0 (cum_* are the caller's to zero).
+ *
+ * USV_ERR_ARG, before any HIP call, for n <= 0, obs_dim <= 0, n_stack < 1, a NULL ring, j < 0,
+ * reward_bytes not 4 / 8 or an unknown flag; then for a missing buffer, one not aligned to its element size (obs rows and
+ * the ring need 4-B alignment only) or not device memory of the ring's device. */
+typedef enum usv_wrap_flags { USV_WRAP_CLEAR_KEEPS_SIGN = 1 } usv_wrap_flags;
+typedef struct usv_wrap {      /* caller-owned device buffers */
+  int32_t n, obs_dim, n_stack, reward_bytes;
+  int32_t flags;               /* usv_wrap_flags */
+  int32_t reserved;            /* 0 */
+  float* ring;                 /* [n][usv_wrap_ring_stride] */
+  double* ep_ret;              /* [n] running episode return */
+  int32_t* ep_len;             /* [n] running episode length */
+  double* episode;             /* [n][2] (r, l), rows of done envs written; may be NULL */
+  double* cum_ret;             /* [n] sums over the emitted episodes; the three may be NULL together */
+  int64_t* cum_len;
+  int64_t* cum_eps;
+} usv_wrap;
+size_t usv_wrap_ring_stride(int32_t obs_dim, int32_t n_stack);   /* floats per env row; host only; 0 if bad */
+size_t usv_wrap_window_offset(int32_t obs_dim, int32_t n_stack, int64_t j);   /* floats; host only */
+int usv_wrap_reset(const usv_wrap* w, int64_t j, const uint8_t* mask_dev, const float* obs_dev, void* stream);
+int usv_wrap_step(const usv_wrap* w, int64_t j, const float* obs_dev, const void* rew_dev,
+                  const uint8_t* done_dev, const float* final_obs_dev, float* final_stack_dev, void* stream);
 
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).

@@ -1,0 +1,318 @@
+"""The fused wrappers on the GPU (gym_usv_amd.wrappers.DeviceWrappers: usv_wrap_step / usv_wrap_reset)
+against the code they replace: ``DeviceFrameStack`` and a torch float64 / int accumulation of the episode
+statistics, driven with the same inputs.  Every comparison is bitwise (tensors compared as integers)."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+SENT32 = 0x7FC0BEEF                                   # a quiet-NaN payload no input and no result has
+SENT64 = 0x7FF8DEADBEEF0123
+
+
+def bits(t):
+    t = t.contiguous()
+    return t.view(torch.int32 if t.element_size() == 4 else torch.int64)
+
+
+def same(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
+
+
+def off_by_one_float(t):
+    """A contiguous copy of float32 `t` whose base is one float past its allocation."""
+    flat = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    flat[1:] = t.flatten()
+    v = flat[1:].view(t.shape)
+    assert v.data_ptr() % 8 == 4 and v.is_contiguous()
+    return v
+
+
+def script(n, d, k, density, rdt, seed):
+    """obs [T + 1, n, d], final [T, n, d], rew [T, n], done [T, n] on the CPU; T = 3k + 2.  density 0.1 has
+    forced repeats: about half of a step's done envs are done again on the next step."""
+    T = 3 * k + 2
+    g = torch.Generator().manual_seed(seed)
+    obs = torch.randn((T + 1, n, d), generator=g)
+    final = torch.randn((T, n, d), generator=g)
+    rew = torch.randn((T, n), generator=g, dtype=torch.float64)
+    rew = rew.to(rdt)
+    if density in (0, 1):
+        done = torch.full((T, n), bool(density))
+    else:
+        done = torch.rand((T, n), generator=g) < density
+        again = torch.rand((T, n), generator=g) < 0.5
+        for t in range(1, T):
+            done[t] |= done[t - 1] & again[t]
+        done[0, 0] = done[1, 0] = True                # at least one repeat, also at n = 1
+    return obs, final, rew, done
+
+
+class RefStats:
+    """ep_ret / ep_len / episode / cum_* as torch ops, in the kernel's order."""
+
+    def __init__(self, n, dev):
+        self.ep_ret = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.ep_len = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.cum_ret = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.cum_len = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.cum_eps = torch.zeros(n, dtype=torch.int64, device=dev)
+
+    def step(self, rew, done):
+        self.ep_ret += rew.to(torch.float64)
+        self.ep_len += 1
+        idx = done.nonzero().flatten()
+        ep = torch.stack((self.ep_ret[idx], self.ep_len[idx].to(torch.float64)), dim=1)
+        self.cum_ret[idx] += self.ep_ret[idx]
+        self.cum_len[idx] += self.ep_len[idx].to(torch.int64)
+        self.cum_eps[idx] += 1
+        self.ep_ret[idx] = 0
+        self.ep_len[idx] = 0
+        return idx, ep
+
+
+def run_scripted(n, d, k, density, rdt, seed, misaligned=False):
+    from gym_usv_amd.sb3 import DeviceFrameStack
+    from gym_usv_amd.wrappers import DeviceWrappers
+    dev = torch.device("cuda", 0)
+    obs, final, rew, done = (t.to(dev) for t in script(n, d, k, density, rdt, seed))
+    wr = DeviceWrappers(n, d, k, dev, rdt)
+    if misaligned:
+        wr.ring = off_by_one_float(wr.ring)
+        wr._bind()
+    give = off_by_one_float if misaligned else (lambda t: t.contiguous())
+    fs = DeviceFrameStack(n, d, k, dev)
+    ref = RefStats(n, dev)
+    assert same(wr.reset(give(obs[0])), fs.reset(obs[0]))
+    emitted = 0
+    for t in range(done.shape[0]):
+        key = f"n {n} d {d} k {k} density {density} {rdt} step {t}"
+        bits(wr.final_stack).fill_(SENT32)
+        bits(wr.episode).fill_(SENT64)
+        want, term = fs.step(obs[t + 1], done[t], final[t])
+        stacked, fstack, episode = wr.step(give(obs[t + 1]), rew[t], done[t], give(final[t]))
+        assert stacked.shape == (n, k * d) and stacked.stride(1) == 1, key
+        assert same(stacked, want), key
+        idx, ep = ref.step(rew[t], done[t])
+        live = ~done[t]
+        if idx.numel():
+            assert same(fstack[idx], term), key
+            assert same(episode[idx], ep), key
+        else:
+            assert term is None, key
+        assert bool((bits(fstack[live]) == SENT32).all()), key       # rows of envs not done: untouched
+        assert bool((bits(episode[live]) == SENT64).all()), key
+        assert same(wr.ep_ret, ref.ep_ret) and same(wr.ep_len, ref.ep_len), key
+        assert same(wr.cum_ret, ref.cum_ret) and same(wr.cum_len, ref.cum_len) and same(wr.cum_eps, ref.cum_eps), key
+        emitted += int(idx.numel())
+    ret, eps, steps = wr.totals()
+    assert eps == emitted and steps == int(ref.cum_len.sum()) and ret == float(ref.cum_ret.sum())
+    assert same(wr.cum_eps, ref.cum_eps)                            # totals() clears nothing
+    if density == 1:
+        assert eps == n * done.shape[0]
+
+
+@pytest.mark.parametrize("k", [1, 2, 5])
+@pytest.mark.parametrize("d", [143, 6])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+def test_scripted_steps_match_frame_stack_and_torch_stats(n, d, k):
+    """3k + 2 steps after a reset; done densities 0, 1 and ~0.1 with repeats; f32 and f64 rewards."""
+    for density in (0, 1, 0.1):
+        for rdt in (torch.float32, torch.float64):
+            run_scripted(n, d, k, density, rdt, seed=n * 1000 + d * 10 + k)
+
+
+def test_scripted_steps_with_a_misaligned_base():
+    """obs, final obs and the ring one float past their allocations (4-B aligned only)."""
+    run_scripted(65, 143, 5, 0.1, torch.float32, seed=5, misaligned=True)
+    run_scripted(257, 6, 2, 0.1, torch.float64, seed=6, misaligned=True)
+
+
+def test_scripted_steps_on_a_side_stream():
+    s = torch.cuda.Stream(0)
+    s.wait_stream(torch.cuda.current_stream(0))
+    with torch.cuda.stream(s):
+        run_scripted(257, 143, 5, 0.1, torch.float32, seed=7)
+    s.synchronize()
+
+
+def test_masked_reset_restarts_masked_rows_only():
+    """A masked reset of a random half of 257 envs mid-sequence: masked rows restart (zeros + the new
+    obs, counters 0) and go on like a wrapper reset in full at that point; the other rows are
+    bit-identical to a run without the reset."""
+    from gym_usv_amd.wrappers import DeviceWrappers
+    n, d, k, at = 257, 143, 5, 4
+    dev = torch.device("cuda", 0)
+    obs, final, rew, done = (t.to(dev) for t in script(n, d, k, 0.1, torch.float32, seed=11))
+    g = torch.Generator().manual_seed(12)
+    mask = (torch.rand(n, generator=g) < 0.5).to(dev)
+    new = torch.randn((n, d), generator=g).to(dev)
+    a, plain, fresh = (DeviceWrappers(n, d, k, dev) for _ in range(3))
+    a.reset(obs[0].contiguous())
+    plain.reset(obs[0].contiguous())
+    for t in range(done.shape[0]):
+        if t == at:
+            st = a.reset(new, mask)
+            want = torch.zeros((n, k * d), device=dev)
+            want[:, -d:] = new
+            assert same(st[mask], want[mask])
+            assert same(st[~mask], plain.stacked[~mask])
+            assert not a.ep_ret[mask].any() and not a.ep_len[mask].any()
+            assert same(a.ep_ret[~mask], plain.ep_ret[~mask]) and same(a.ep_len[~mask], plain.ep_len[~mask])
+            fresh.reset(new)
+        args = (obs[t + 1].contiguous(), rew[t].contiguous(), done[t].contiguous(), final[t].contiguous())
+        outs = [w.step(*args) for w in ((a, plain, fresh) if t >= at else (a, plain))]
+        if t < at:
+            continue
+        (sa, fa, ea), (sp, fp, ep), (sf, ff, ef) = outs
+        dn = done[t]
+        for rows, other, so, fo, eo in ((~mask, plain, sp, fp, ep), (mask, fresh, sf, ff, ef)):
+            assert same(sa[rows], so[rows]), t
+            assert same(fa[rows & dn], fo[rows & dn]) and same(ea[rows & dn], eo[rows & dn]), t
+            assert same(a.ep_ret[rows], other.ep_ret[rows]) and same(a.ep_len[rows], other.ep_len[rows]), t
+    assert same(a.cum_eps[~mask], plain.cum_eps[~mask]) and same(a.cum_ret[~mask], plain.cum_ret[~mask])
+
+
+@pytest.mark.parametrize("precision", ["f32", "f64"])
+def test_real_env_with_fused_wrappers_matches_frame_stack(precision):
+    """usv-simple, 256 envs, TimeLimit 7 (every env resets five times in 40 steps): UsvVectorEnv +
+    DeviceWrappers against UsvVectorEnv + DeviceFrameStack + torch statistics, same seed and actions."""
+    import gym_usv_amd
+    from gym_usv_amd.sb3 import DeviceFrameStack
+    from gym_usv_amd.wrappers import DeviceWrappers
+    n, k, steps = 256, 5, 40
+    dev = torch.device("cuda", 0)
+    ea = gym_usv_amd.make_vec("usv-simple", n, seed=3, precision=precision, max_episode_steps=7, copy=False)
+    eb = gym_usv_amd.make_vec("usv-simple", n, seed=3, precision=precision, max_episode_steps=7)
+    d = ea.obs_dim
+    wr = DeviceWrappers(n, d, k, dev, ea.reward.dtype)
+    fs, ref = DeviceFrameStack(n, d, k, dev), RefStats(n, dev)
+    oa, _ = ea.reset(seed=3)
+    ob, _ = eb.reset(seed=3)
+    assert same(wr.reset(oa), fs.reset(ob))
+    rng = np.random.default_rng(0)
+    resets = torch.zeros(n, dtype=torch.int64, device=dev)
+    for t in range(steps):
+        act = torch.from_numpy(rng.uniform([0.2, -1], [1, 1], size=(n, 2)).astype(np.float32)).to(dev)
+        oa, ra, _, _, ia = ea.step(act)
+        ob, rb, _, _, ib = eb.step(act)
+        dn = ib["_final_obs"]
+        assert same(ia["_final_obs"], dn) and same(ra, rb), t
+        stacked, fstack, episode = wr.step(oa, ra, ia["_final_obs"], ia["final_obs"])
+        want, term = fs.step(ob, dn, ib["final_obs"])
+        assert same(stacked, want), t
+        idx, ep = ref.step(rb, dn)
+        if idx.numel():
+            assert same(fstack[idx], term) and same(episode[idx], ep), t
+        assert same(wr.ep_ret, ref.ep_ret) and same(wr.ep_len, ref.ep_len), t
+        resets += dn
+    assert int(resets.min()) >= 5
+    assert same(wr.cum_eps, resets) and same(wr.cum_ret, ref.cum_ret) and same(wr.cum_len, ref.cum_len)
+    ea.close()
+    eb.close()
+
+
+_ADAPTER_RUN = []
+
+
+def adapter_run():
+    """One rollout of Sb3VecEnv(fused=False) and Sb3VecEnv(fused=True) side by side (usv-simple, 256 envs,
+    k = 5, TimeLimit 7, 40 steps, same seed and actions), shared by the tests below: per step
+    (obs, rew, done, infos) of each, copied."""
+    if _ADAPTER_RUN:
+        return _ADAPTER_RUN[0]
+    from gym_usv_amd.sb3 import DeviceFrameStack, Sb3VecEnv
+    from gym_usv_amd.wrappers import DeviceWrappers
+    n, k, steps = 256, 5, 40
+    plain = Sb3VecEnv("usv-simple", num_envs=n, frame_stack=k, seed=2, max_episode_steps=7)
+    fused = Sb3VecEnv("usv-simple", num_envs=n, frame_stack=k, seed=2, max_episode_steps=7, fused=True)
+    assert isinstance(plain._stack, DeviceFrameStack) and plain._wrap is None      # the default is unchanged
+    assert isinstance(fused._wrap, DeviceWrappers) and fused._stack is None
+    assert fused.observation_space.shape == plain.observation_space.shape == (k * 143,)
+    op, of = plain.reset(), fused.reset()
+    assert op.shape == of.shape == (n, k * 143) and np.array_equal(op.view(np.uint32), of.view(np.uint32))
+    rng = np.random.default_rng(1)
+    rec = []
+    for t in range(steps):
+        act = rng.uniform([0.2, -1], [1, 1], size=(n, 2)).astype(np.float32)
+        rec.append(tuple((o.copy(), r.copy(), d.copy(), i) for o, r, d, i in (plain.step(act), fused.step(act))))
+    plain.close()
+    fused.close()
+    _ADAPTER_RUN.append(rec)
+    return rec
+
+
+def test_fused_adapter_equals_the_default_adapter():
+    """Sb3VecEnv(fused=True) against Sb3VecEnv(fused=False): obs, rewards and dones bitwise, and every info
+    dict (TimeLimit.truncated, episode r and l exactly; terminal_observation bitwise in the next test).
+    Bitwise includes the sign of zeros: the default adapter clears a done env's stack by multiplying with
+    the mask, which leaves -0.0 where the old frame was negative, and the fused mode asks the kernel for
+    the same (clear_keeps_sign)."""
+    episodes = 0
+    for t, ((op, rp, dp, ip), (of, rf, df, inf)) in enumerate(adapter_run()):
+        n = len(dp)
+        assert np.array_equal(op.view(np.uint32), of.view(np.uint32)) and not np.isnan(op).any(), t
+        assert np.array_equal(rp.view(np.uint32), rf.view(np.uint32)) and np.array_equal(dp, df), t
+        assert len(ip) == len(inf) == n
+        for i in range(n):
+            a, b = ip[i], inf[i]
+            assert set(a) == set(b), (t, i)
+            if not a:
+                assert not dp[i]
+                continue
+            episodes += 1
+            ta, tb = a["terminal_observation"], b["terminal_observation"]
+            assert ta.dtype == tb.dtype == np.float32 and ta.shape == tb.shape
+            assert a["TimeLimit.truncated"] is b["TimeLimit.truncated"], (t, i)
+            assert a["episode"]["r"] == b["episode"]["r"] and a["episode"]["l"] == b["episode"]["l"], (t, i)
+            assert type(b["episode"]["l"]) is int and set(b["episode"]) == {"r", "l", "t"}
+    assert episodes >= 5 * 256
+
+
+def test_fused_adapter_terminal_observation_bitwise():
+    """Every terminal_observation of the fused adapter bitwise equal to the default adapter's: 1 291
+    terminal rows, 923 065 words in this rollout.  Ten of them are -0.0: frames of an env that ended
+    twice within k steps, cleared by the default adapter's mask multiply the first time and shown by the
+    second terminal observation; with a clear that stores +0.0 those ten words differ."""
+    rows = words = diff = negzero = 0
+    for (_, _, _, ip), (_, _, _, inf) in adapter_run():
+        for a, b in zip(ip, inf):
+            if a:
+                ua, ub = a["terminal_observation"].view(np.uint32), b["terminal_observation"].view(np.uint32)
+                rows += 1
+                words += ua.size
+                diff += int((ua != ub).sum())
+                negzero += int((ua == 0x80000000).sum())
+    print(f"terminal_observation rows {rows}, words {words}, bitwise different {diff}, -0.0 words {negzero}")
+    assert rows >= 5 * 256 and diff == 0, f"{diff} of {words} words in {rows} rows differ"
+    assert negzero > 0                                 # the rollout does exercise the sign of a cleared frame
+
+
+@pytest.mark.parametrize("n,d,k", [(65, 143, 5), (257, 6, 2), (64, 143, 1)])
+def test_clear_keeps_sign_equals_a_mask_multiply(n, d, k):
+    """DeviceWrappers(clear_keeps_sign=True) against the stack update of Sb3VecEnv's default path restated
+    in torch (roll, multiply by ~done, push; terminal rows from the stack before the multiply), bitwise,
+    over 3k + 2 steps with repeated dones; the statistics do not depend on the flag."""
+    from gym_usv_amd.wrappers import DeviceWrappers
+    dev = torch.device("cuda", 0)
+    obs, final, rew, done = (t.to(dev) for t in script(n, d, k, 0.1, torch.float32, seed=99 + n))
+    wr = DeviceWrappers(n, d, k, dev, clear_keeps_sign=True)
+    ref = RefStats(n, dev)
+    buf = torch.zeros((n, k * d), device=dev)
+    buf[:, -d:] = obs[0]
+    assert same(wr.reset(obs[0].contiguous()), buf)
+    negzero = 0
+    for t in range(done.shape[0]):
+        dn = done[t]
+        new = torch.empty_like(buf)
+        torch.mul(buf[:, d:], (~dn)[:, None], out=new[:, :-d])
+        new[:, -d:] = obs[t + 1]
+        stacked, fstack, episode = wr.step(obs[t + 1].contiguous(), rew[t], dn, final[t].contiguous())
+        assert same(stacked, new), t
+        idx, ep = ref.step(rew[t], dn)
+        assert same(fstack[idx], torch.cat((buf[idx, d:], final[t][idx]), dim=1)), t
+        assert same(episode[idx], ep) and same(wr.ep_ret, ref.ep_ret) and same(wr.ep_len, ref.ep_len), t
+        negzero += int((bits(new) == -(1 << 31)).sum())
+        buf = new
+    assert negzero > 0 or k == 1
