@@ -16,6 +16,8 @@
 //   usv_noscan_step.hpp   scan-free step (ignore_obstacles)
 //   usv_wrap_layout.hpp   the fused wrappers' frame ring: slots, stride, window (host C++, no HIP)
 //   usv_wrap.hpp          frame stack + episode statistics behind the step (usv_wrap_step / _reset)
+//   usv_norm_math.hpp     VecNormalize: moments arithmetic, work split, transform (host C++, no HIP)
+//   usv_norm.hpp          VecNormalize in front of the frame stack (usv_wrap_step_norm / _reset_norm)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -40,6 +42,7 @@
 #include "usv_legacy.hpp"
 #include "usv_noscan_step.hpp"   // (after the others: the kernels before it keep their place in the code object)
 #include "usv_wrap.hpp"
+#include "usv_norm.hpp"
 
 
 // ============================================================================= host side
@@ -921,6 +924,128 @@ int usv_wrap_step(const usv_wrap* w, int64_t j, const float* obs, const void* re
   else
     hipLaunchKernelGGL(wrap_step_kernel<float>, grid, block, 0, (hipStream_t)stream, a, obs, (const float*)rew,
                        done, fobs, final_stack);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- fused VecNormalize (usv_norm.hpp) in front of the frame stack
+size_t usv_norm_scratch_bytes(int32_t n, int32_t obs_dim) {
+  return n > 0 && obs_dim > 0 ? (size_t)2 * norm_num_partials(n) * ((size_t)obs_dim + 1) * sizeof(double) : 0;
+}
+
+// The checks that need no HIP call; the device of every pointer is wrap_args's to check (norm_ptrs).
+static int norm_check(const usv_wrap* w, const usv_norm* z) {
+  if (!z) return fail(USV_ERR_ARG, "null usv_norm");
+  if (z->n <= 0 || z->obs_dim <= 0) return fail(USV_ERR_ARG, "usv_norm: n and obs_dim must be > 0");
+  if (z->obs_dim > kNormMaxDim) return fail(USV_ERR_ARG, "usv_norm: obs_dim above 4096 (the tables are staged in LDS)");
+  if (w && (z->n != w->n || z->obs_dim != w->obs_dim))
+    return fail(USV_ERR_ARG, "usv_norm: n and obs_dim must equal the usv_wrap's");
+  if ((z->flags & ~(USV_NORM_TRAINING | USV_NORM_OBS | USV_NORM_REWARD)) != 0 || z->reserved != 0)
+    return fail(USV_ERR_ARG, "usv_norm: unknown flags");
+  if (!(z->clip_obs >= 0.0) || !(z->clip_reward >= 0.0)) return fail(USV_ERR_ARG, "usv_norm: clip_obs and clip_reward must be >= 0");
+  if (!(z->gamma >= 0.0 && z->gamma <= 1.0)) return fail(USV_ERR_ARG, "usv_norm: gamma must be in [0, 1]");
+  if (!(z->epsilon > 0.0)) return fail(USV_ERR_ARG, "usv_norm: epsilon must be > 0");
+  const void* const ptrs[] = {z->obs_mean, z->obs_var, z->obs_inv_std, z->obs_count, z->ret_mean, z->ret_var,
+                              z->ret_inv_std, z->ret_count, z->returns, z->scratch};
+  for (const void* p : ptrs) {
+    if (!p) return fail(USV_ERR_ARG, "usv_norm: null buffer");
+    if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return fail(USV_ERR_ARG, "usv_norm: a buffer is not 8-B aligned");
+  }
+  return USV_OK;
+}
+
+static NormArgs norm_args(const usv_norm* z, bool update) {
+  const bool tr = update && (z->flags & USV_NORM_TRAINING) != 0;
+  return NormArgs{z->n, z->obs_dim, tr && (z->flags & USV_NORM_OBS) != 0, tr && (z->flags & USV_NORM_REWARD) != 0,
+                  (z->flags & USV_NORM_REWARD) != 0, z->clip_obs, z->clip_reward, z->gamma, z->epsilon,
+                  z->obs_mean, z->obs_var, z->obs_inv_std, z->obs_count, z->ret_mean, z->ret_var, z->ret_inv_std,
+                  z->ret_count, z->returns, z->scratch};
+}
+
+// Launches 1 and 2 of usv_norm.hpp (nothing if the call updates no statistic).
+extern "C++" {
+template <typename RW>
+static void norm_reduce(const NormArgs& z, const float* obs, const RW* rew, hipStream_t s) {
+  if (!z.upd_obs && !z.upd_ret) return;
+  const int P = norm_num_partials(z.n);
+  hipLaunchKernelGGL(norm_moments_kernel<RW>, dim3(P), dim3(kBlock), 0, s, z, obs, rew);
+  hipLaunchKernelGGL(norm_finalise_kernel, dim3(z.D + 1), dim3(kNormLanes), 0, s, z, P);
+}
+}
+
+int usv_wrap_reset_norm(const usv_wrap* w, const usv_norm* zn, int64_t j, const uint8_t* mask, const float* obs,
+                        void* stream) {
+  WrapArgs a;
+  int dev;
+  if (int rc = norm_check(w, zn)) return rc;
+  if (int rc = wrap_args(w, j, {obs, zn->obs_mean, zn->obs_var, zn->obs_inv_std, zn->obs_count, zn->ret_mean,
+                                zn->ret_var, zn->ret_inv_std, zn->ret_count, zn->returns, zn->scratch}, a, dev))
+    return rc;
+  if (mask) {
+    hipPointerAttribute_t pa{};
+    if (hipPointerGetAttributes(&pa, mask) != hipSuccess || pa.device != dev) {
+      (void)hipGetLastError();
+      return fail(USV_ERR_ARG, "usv_wrap: mask is not a device pointer on the ring's device");
+    }
+  }
+  if ((reinterpret_cast<uintptr_t>(obs) & 3) != 0) return fail(USV_ERR_ARG, "usv_wrap: obs is not 4-B aligned");
+  DeviceGuard g(dev);
+  NormArgs z = norm_args(zn, mask == nullptr);          // a masked reset updates no statistic
+  z.upd_ret = 0;
+  const hipStream_t s = (hipStream_t)stream;
+  norm_reduce<float>(z, obs, nullptr, s);
+  const int per_block = kWaves * kWrapEnvs;
+  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
+  const bool no = (zn->flags & USV_NORM_OBS) != 0;
+  const size_t lds = no ? (size_t)16 * a.D : 0;
+  if (mask) {
+    if (no) hipLaunchKernelGGL((wrap_reset_norm_kernel<true, true>), grid, block, lds, s, a, z, mask, obs);
+    else hipLaunchKernelGGL((wrap_reset_norm_kernel<true, false>), grid, block, lds, s, a, z, mask, obs);
+  } else {
+    if (no) hipLaunchKernelGGL((wrap_reset_norm_kernel<false, true>), grid, block, lds, s, a, z, mask, obs);
+    else hipLaunchKernelGGL((wrap_reset_norm_kernel<false, false>), grid, block, lds, s, a, z, mask, obs);
+  }
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_wrap_step_norm(const usv_wrap* w, const usv_norm* zn, int64_t j, const float* obs, const void* rew,
+                       const uint8_t* done, const float* final_obs, float* final_stack, float* norm_rew_out,
+                       void* stream) {
+  WrapArgs a;
+  int dev;
+  if (int rc = norm_check(w, zn)) return rc;
+  if (final_stack && !final_obs && w && w->n > 0 && w->obs_dim > 0 && w->n_stack >= 1 && w->ring)
+    return fail(USV_ERR_ARG, "usv_wrap_step: final_stack needs final_obs");
+  const void* const fo = final_stack ? (const void*)final_obs : (const void*)obs;   // checked only with final_stack
+  const void* const fs = final_stack ? (const void*)final_stack : (const void*)obs;
+  if (int rc = wrap_args(w, j, {obs, rew, done, fo, fs, norm_rew_out, zn->obs_mean, zn->obs_var, zn->obs_inv_std,
+                                zn->obs_count, zn->ret_mean, zn->ret_var, zn->ret_inv_std, zn->ret_count, zn->returns,
+                                zn->scratch}, a, dev))
+    return rc;
+  auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
+  if (misaligned(obs, 4) || misaligned(rew, a.reward_bytes) || misaligned(norm_rew_out, 4) ||
+      (final_stack && (misaligned(final_obs, 4) || misaligned(final_stack, 4))))
+    return fail(USV_ERR_ARG, "usv_wrap_step: a buffer is not aligned to its element size");
+  DeviceGuard g(dev);
+  const NormArgs z = norm_args(zn, true);
+  const hipStream_t s = (hipStream_t)stream;
+  const int per_block = kWaves * kWrapEnvs;
+  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
+  const float* const fobs = final_stack ? final_obs : nullptr;
+  const bool no = (zn->flags & USV_NORM_OBS) != 0;
+  const size_t lds = no ? (size_t)16 * a.D : 0;
+  if (a.reward_bytes == 8) {
+    const double* const r = (const double*)rew;
+    norm_reduce<double>(z, obs, r, s);
+    if (no) hipLaunchKernelGGL((wrap_step_norm_kernel<double, true>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
+    else hipLaunchKernelGGL((wrap_step_norm_kernel<double, false>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
+  } else {
+    const float* const r = (const float*)rew;
+    norm_reduce<float>(z, obs, r, s);
+    if (no) hipLaunchKernelGGL((wrap_step_norm_kernel<float, true>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
+    else hipLaunchKernelGGL((wrap_step_norm_kernel<float, false>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
+  }
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

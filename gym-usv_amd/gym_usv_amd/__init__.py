@@ -36,8 +36,12 @@ def make_vec(env_id, num_envs, **kwargs):
     return UsvVectorEnv(env_id, num_envs=num_envs, **kwargs)
 
 
-def make_sb3_vec_env(env_id, n_envs, frame_stack=0, seed=0, **kwargs):
+def make_sb3_vec_env(env_id, n_envs, frame_stack=0, seed=0, normalize=None, **kwargs):
     """SB3 ``VecEnv`` counterpart of ``VecFrameStack(make_vec_env(env_id, n_envs), frame_stack)``
-    (train_test/sb3_train_vec.py:67-70): one HIP-stepped batch with Monitor/TimeLimit infos."""
+    (train_test/sb3_train_vec.py:67-70): one HIP-stepped batch with Monitor/TimeLimit infos.
+    ``normalize`` (a dict of ``VecNormalize`` settings, ``{}`` for SB3's defaults; needs ``fused=True``)
+    puts ``VecNormalize`` under the frame stack: ``VecFrameStack(VecNormalize(...), frame_stack)``."""
     from .sb3 import Sb3VecEnv
+    if normalize is not None:
+        kwargs["normalize"] = normalize
     return Sb3VecEnv(env_id, num_envs=n_envs, frame_stack=frame_stack, seed=seed, **kwargs)

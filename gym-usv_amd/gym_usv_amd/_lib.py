@@ -68,6 +68,20 @@ class UsvWrap(ctypes.Structure):
                 ("cum_len", ctypes.c_void_p), ("cum_eps", ctypes.c_void_p)]
 
 
+NORM_TRAINING, NORM_OBS, NORM_REWARD = 1, 2, 4
+
+
+class UsvNorm(ctypes.Structure):
+    """usv_norm: the caller-owned statistics of the fused VecNormalize (usv_wrap_step_norm / _reset_norm)."""
+    _fields_ = [("n", ctypes.c_int32), ("obs_dim", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("clip_obs", ctypes.c_double), ("clip_reward", ctypes.c_double),
+                ("gamma", ctypes.c_double), ("epsilon", ctypes.c_double),
+                ("obs_mean", ctypes.c_void_p), ("obs_var", ctypes.c_void_p), ("obs_inv_std", ctypes.c_void_p),
+                ("obs_count", ctypes.c_void_p), ("ret_mean", ctypes.c_void_p), ("ret_var", ctypes.c_void_p),
+                ("ret_inv_std", ctypes.c_void_p), ("ret_count", ctypes.c_void_p), ("returns", ctypes.c_void_p),
+                ("scratch", ctypes.c_void_p)]
+
+
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
 _i64 = ctypes.c_int64
@@ -104,6 +118,10 @@ SIGNATURES = [
     ("usv_wrap_window_offset", _sz, [_i32, _i32, _i64]),
     ("usv_wrap_reset", ctypes.c_int, [ctypes.POINTER(UsvWrap), _i64, _vp, _vp, _vp]),
     ("usv_wrap_step", ctypes.c_int, [ctypes.POINTER(UsvWrap), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_norm_scratch_bytes", _sz, [_i32, _i32]),
+    ("usv_wrap_step_norm", ctypes.c_int, [ctypes.POINTER(UsvWrap), ctypes.POINTER(UsvNorm), _i64, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp]),
+    ("usv_wrap_reset_norm", ctypes.c_int, [ctypes.POINTER(UsvWrap), ctypes.POINTER(UsvNorm), _i64, _vp, _vp, _vp]),
 ]
 
 _LIBS = {}

@@ -105,10 +105,23 @@ class Sb3VecEnv:
     ``fused=True`` computes the frame stack and the Monitor statistics with one HIP launch per step
     (``gym_usv_amd.wrappers.DeviceWrappers``: a mirrored frame ring, nothing shifted) instead of the
     torch ops of the default path; the returned arrays and infos are the same, bit for bit.  It needs the HIP library
-    and a GPU ``venv``: ``UsvLibError`` otherwise (no CPU fallback)."""
+    and a GPU ``venv``: ``UsvLibError`` otherwise (no CPU fallback).
+
+    ``normalize`` (with ``fused=True``; a dict of SB3 ``VecNormalize`` settings, ``{}`` for its defaults)
+    makes this ``VecFrameStack(VecNormalize(venv))``: observations, rewards and ``terminal_observation``
+    come back normalised, ``info["episode"]["r"]`` stays raw (the Monitor is inside), and the usual
+    ``VecNormalize`` surface is there: ``obs_rms`` / ``ret_rms``, ``training`` / ``norm_reward`` (also
+    through ``set_attr``), ``get_original_obs()`` / ``get_original_reward()``, ``save`` / ``load`` (.npz).
+    A done env's stack is then cleared to +0.0 as SB3 does.  The statistics live on the device and
+    belong to this process."""
+
+    _NORM_ATTRS = ("training", "norm_obs", "norm_reward")
 
     def __init__(self, env_id="usv-simple", num_envs=4096, frame_stack=0, seed=0, venv=None,
-                 fresh_infos=False, fused=False, **kw):
+                 fresh_infos=False, fused=False, normalize=None, **kw):
+        if normalize is not None and not fused:
+            raise ValueError("normalize needs fused=True: the running statistics and the transform are part of "
+                             "the fused wrappers' HIP launches, the torch path of this adapter has no counterpart")
         if venv is None:
             from .vector_env import UsvVectorEnv
             # each step is consumed (copied to the host) before the next: the persistent buffers do
@@ -127,8 +140,11 @@ class Sb3VecEnv:
             rdt = venv.reward.dtype if hasattr(venv, "reward") else torch.float32
             # clear_keeps_sign: a done env's stack cleared as _step_wait's mask multiply clears it (x * 0),
             # so that both modes return the same bits, the sign of a cleared frame's zeros included
+            # (with normalize there is no unfused path to equal: +0.0, SB3's stacked_obs[i] = 0)
             self._wrap = DeviceWrappers(self.num_envs, d, frame_stack or 1, venv.device, rdt,
-                                        clear_keeps_sign=True)
+                                        clear_keeps_sign=normalize is None, normalize=normalize)
+        self._norm = normalize is not None
+        self._raw_obs = self._raw_rew = None
         self._frame_stack = frame_stack
         obs_space = venv.single_observation_space
         if frame_stack:
@@ -168,8 +184,9 @@ class Sb3VecEnv:
         if self._stack is not None:
             obs = self._stack.reset(obs)
         if self._wrap is not None:
+            self._raw_obs = obs
             stacked = self._wrap.reset(obs)
-            obs = stacked if self._frame_stack else obs
+            obs = stacked if self._frame_stack or self._norm else obs
         return obs.cpu().numpy()
 
     def step_async(self, actions):
@@ -266,7 +283,10 @@ class Sb3VecEnv:
         obs, rew, term, trunc, info = venv.step(self._act_dev)
         done = info["_final_obs"]
         stacked, fstack, episode = self._wrap.step(obs, rew, done, info["final_obs"])
-        if self._frame_stack:
+        if self._norm:
+            self._raw_obs, self._raw_rew = obs, rew     # get_original_obs / _reward
+            rew = self._wrap.norm_rew
+        if self._frame_stack or self._norm:
             obs = stacked                               # a window of the ring, valid until the next step
         h = self._host[self._hb]
         self._hb ^= 1
@@ -330,7 +350,67 @@ class Sb3VecEnv:
         return [val] * len(self._indices(indices))
 
     def set_attr(self, attr_name, value, indices=None):
+        if self._norm and attr_name in self._NORM_ATTRS:
+            setattr(self._wrap, attr_name, bool(value))
+            return
         setattr(self.venv, attr_name, value)
+
+    # ---------------------------------------------------------------- VecNormalize surface (normalize=)
+    def _need_norm(self):
+        if not self._norm:
+            raise AttributeError("this Sb3VecEnv was built without normalize=")
+        return self._wrap
+
+    training = property(lambda self: self._need_norm().training,
+                        lambda self, v: setattr(self._need_norm(), "training", bool(v)))
+    norm_obs = property(lambda self: self._need_norm().norm_obs,
+                        lambda self, v: setattr(self._need_norm(), "norm_obs", bool(v)))
+    norm_reward = property(lambda self: self._need_norm().norm_reward,
+                           lambda self, v: setattr(self._need_norm(), "norm_reward", bool(v)))
+
+    class _Rms:
+        """``RunningMeanStd``'s three attributes as NumPy copies of the device statistics."""
+
+        def __init__(self, mean, var, count):
+            self.mean, self.var, self.count = mean, var, count
+
+    @property
+    def obs_rms(self):
+        w = self._need_norm()
+        return self._Rms(w.obs_mean.cpu().numpy(), w.obs_var.cpu().numpy(), float(w.obs_count.cpu()[0]))
+
+    @property
+    def ret_rms(self):
+        w = self._need_norm()
+        return self._Rms(w.ret_mean.cpu().numpy()[0], w.ret_var.cpu().numpy()[0], float(w.ret_count.cpu()[0]))
+
+    def get_original_obs(self):
+        """The raw (un-normalised, un-stacked) obs [N, D] of the last step or reset."""
+        self._need_norm()
+        return self._raw_obs.cpu().numpy()
+
+    def get_original_reward(self):
+        """The raw rewards of the last step, float32."""
+        self._need_norm()
+        if self._raw_rew is None:
+            raise RuntimeError("get_original_reward: no step has been taken yet")
+        return self._raw_rew.to(torch.float32).cpu().numpy()
+
+    def normalize_obs(self, obs):
+        return self._need_norm().normalize_obs(torch.as_tensor(obs, device=self.venv.device)).cpu().numpy()
+
+    def normalize_reward(self, reward):
+        return self._need_norm().normalize_reward(torch.as_tensor(reward, device=self.venv.device)).cpu().numpy()
+
+    def save(self, path):
+        """The running statistics as an ``.npz`` (``VecNormalize.save`` without pickle)."""
+        np.savez(path, **{k: v.cpu().numpy() for k, v in self._need_norm().state_dict().items()})
+
+    def load(self, path):
+        """Statistics written by ``save`` (of this or another adapter) into this one."""
+        w = self._need_norm()
+        with np.load(path) as f:
+            w.load_state_dict({k: torch.from_numpy(f[k]).to(w.device) for k in f.files})
 
     def env_method(self, method_name, *args, indices=None, **kwargs):
         raise NotImplementedError("per-env methods: the envs are one batched GPU object")

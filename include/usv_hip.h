@@ -326,6 +326,74 @@ int usv_wrap_reset(const usv_wrap* w, int64_t j, const uint8_t* mask_dev, const 
 int usv_wrap_step(const usv_wrap* w, int64_t j, const float* obs_dev, const void* rew_dev,
                   const uint8_t* done_dev, const float* final_obs_dev, float* final_stack_dev, void* stream);
 
+/* Fused VecNormalize: SB3's VecNormalize (stable_baselines3/common/vec_env/vec_normalize.py) between the
+ * step and the frame stack, VecFrameStack(VecNormalize(venv)), for all envs behind usv_step on the same
+ * stream with no host sync.  Additive and handle-free like usv_wrap_* (ABI v5 addition).  usv_norm holds
+ * the caller-owned statistics; start them as RunningMeanStd.__init__ does: mean = 0, var = 1,
+ * count = 1e-4 (running_mean_std.py), returns = 0.
+ *
+ * usv_wrap_step_norm = usv_wrap_step with, in this order (flags: T = USV_NORM_TRAINING, O = USV_NORM_OBS,
+ * R = USV_NORM_REWARD):
+ *   1. T and O: obs_rms.update(obs_dev), per column of the [n][obs_dim] obs the step wrote (a done env's
+ *      row is its reset obs, as in DummyVecEnv)                    <- step_wait: self.obs_rms.update(obs)
+ *   2. T and R: returns = returns * gamma + reward in f64, then ret_rms.update(returns)
+ *                                                                  <- step_wait: _update_reward
+ *   update = RunningMeanStd.update_from_moments with the batch mean, population variance and count n:
+ *     delta = bm - mean; tot = count + n; mean += delta n / tot;
+ *     M2 = var count + bv n + delta^2 count n / tot; var = M2 / tot; count = tot.
+ *   3. obs_inv_std[c] = 1 / sqrt(obs_var[c] + epsilon), ret_inv_std = 1 / sqrt(ret_var + epsilon) are
+ *      published (f64), from the statistics as they stand after 1 and 2 (or as stored, with T off)
+ *   4. frame j = float(clamp((double(obs) - obs_mean[c]) * obs_inv_std[c], -clip_obs, clip_obs)) with O,
+ *      the raw obs without                                         <- normalize_obs
+ *   5. the final obs of a done env is transformed like 4 before it becomes the last frame of
+ *      final_stack; the older frames are the ring's, normalised when they were pushed
+ *   6. norm_rew_out[e] = float(clamp(double(reward) * ret_inv_std, -clip_reward, clip_reward)) with R
+ *      (no mean is subtracted), float(reward) without              <- normalize_reward
+ *   7. returns[e] = 0 for done envs                                <- step_wait: self.returns[dones] = 0
+ *   8. ep_ret, episode and cum_* use the raw reward (the Monitor sits inside VecNormalize); the clear of a
+ *      done env's stack and the ring layout are usv_wrap_step's.
+ * Deviation from SB3: 4 to 6 multiply by the published reciprocal where SB3 divides by
+ * sqrt(var + epsilon); the value before the rounding to f32 differs by at most one f64 ulp.  In return
+ * the outputs are a bit-exact function of the published obs_mean / obs_inv_std / ret_inv_std:
+ * ((x.astype(f64) - mean) * inv).clip(-c, c).astype(f32) in NumPy gives the same bits.
+ * The batch moments are accumulated as (count, mean, M2) in f64, combined in a fixed order (no atomics):
+ * two calls on the same input give the same bits.  With T on (and O or R) the call is three launches
+ * (partial moments, finalise, normalising step), otherwise one.
+ *
+ * usv_wrap_reset_norm = usv_wrap_reset with returns = 0 for the restarted envs and frame j normalised.
+ * mask_dev == NULL (VecNormalize.reset): with T and O the statistics are first updated with obs_dev.
+ * A masked reset (no SB3 counterpart) updates no statistic and uses the current ones.
+ * The statistics are per process: no collective is involved (a multi-GPU run keeps one set per rank).
+ *
+ * USV_ERR_ARG as for usv_wrap_*, and before any HIP call for a NULL usv_norm, n / obs_dim <= 0 or not
+ * the usv_wrap's, obs_dim > 4096, unknown flags, a negative (or NaN) clip, gamma outside [0, 1],
+ * epsilon <= 0, a NULL buffer or one not 8-B aligned; then for a buffer that is not device memory of the
+ * ring's device.  scratch needs usv_norm_scratch_bytes(n, obs_dim) bytes and is overwritten by every
+ * updating call. */
+typedef enum usv_norm_flags { USV_NORM_TRAINING = 1, USV_NORM_OBS = 2, USV_NORM_REWARD = 4 } usv_norm_flags;
+typedef struct usv_norm {      /* caller-owned device buffers, all f64 */
+  int32_t n, obs_dim;
+  int32_t flags;               /* usv_norm_flags */
+  int32_t reserved;            /* 0 */
+  double clip_obs, clip_reward, gamma, epsilon;   /* SB3 defaults: 10, 10, 0.99, 1e-8 */
+  double* obs_mean;            /* [obs_dim] */
+  double* obs_var;             /* [obs_dim] */
+  double* obs_inv_std;         /* [obs_dim], written by every call */
+  double* obs_count;           /* [1] */
+  double* ret_mean;            /* [1] (kept as RunningMeanStd keeps it; not used by the transform) */
+  double* ret_var;             /* [1] */
+  double* ret_inv_std;         /* [1], written by every call */
+  double* ret_count;           /* [1] */
+  double* returns;             /* [n] discounted return per env */
+  double* scratch;             /* usv_norm_scratch_bytes(n, obs_dim) */
+} usv_norm;
+size_t usv_norm_scratch_bytes(int32_t n, int32_t obs_dim);   /* host only; 0 if bad */
+int usv_wrap_step_norm(const usv_wrap* w, const usv_norm* z, int64_t j, const float* obs_dev, const void* rew_dev,
+                       const uint8_t* done_dev, const float* final_obs_dev, float* final_stack_dev,
+                       float* norm_rew_out_dev, void* stream);
+int usv_wrap_reset_norm(const usv_wrap* w, const usv_norm* z, int64_t j, const uint8_t* mask_dev,
+                        const float* obs_dev, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
