@@ -18,7 +18,13 @@ this image, so this is a compact PPO with the same hyper-parameters where they c
   clipping;
 * TimeLimit truncation bootstrapped from the terminal observation's value for envs that were
   truncated and not terminated (SB3: ``infos[i]["terminal_observation"]`` and
-  ``TimeLimit.truncated``); VecFrameStack(5) via ``DeviceFrameStack``.
+  ``TimeLimit.truncated``); VecFrameStack(5) via ``DeviceFrameStack``;
+* ``--fused`` (``train(fused=True)``): the frame stack and the episode statistics are
+  ``DeviceWrappers`` and the rollout buffer, the truncation bootstrap and the GAE are
+  ``DeviceRollout`` (HIP kernels behind the step, gym_usv_amd/rollout.py).  The policy reads the ring's
+  window in place, the terminal observations are valued in one batch after the rollout, and a rollout
+  makes no host sync: no ``.any()``, ``.nonzero()`` or ``bool()`` on a device tensor.  The buffer
+  arithmetic is then SB3's float32 RolloutBuffer bit for bit; the default path is unchanged.
 
 Rollout size at 4096 envs.  config_ppo's ``n_steps=2048, batch_size=64`` are for the reference's 4
 envs: 8 192 samples per update in 128 minibatches.  With 4096 envs the same n_steps would put 8.4 M
@@ -75,15 +81,16 @@ class ActorCritic(nn.Module):
         shape = (hidden[-1], act_dim) if use_sde else (act_dim,)
         self.log_std = nn.Parameter(torch.full(shape, float(log_std_init)))
 
-    def dist(self, obs):
-        """(Normal over actions, latent_sde)."""
+    def dist(self, obs, validate=None):
+        """(Normal over actions, latent_sde).  ``validate=False`` skips torch.distributions' argument
+        checks, each of which asks the host ``bool(valid.all())``: a stream drain."""
         lat = self.pi_body(obs)
         mean = self.mu(lat)
         if not self.use_sde:
-            return torch.distributions.Normal(mean, self.log_std.exp().expand_as(mean)), None
+            return torch.distributions.Normal(mean, self.log_std.exp().expand_as(mean), validate_args=validate), None
         lat_sde = lat.detach()
         var = (lat_sde * lat_sde) @ (self.log_std.exp() ** 2)
-        return torch.distributions.Normal(mean, torch.sqrt(var + SDE_EPS)), lat_sde
+        return torch.distributions.Normal(mean, torch.sqrt(var + SDE_EPS), validate_args=validate), lat_sde
 
     def sample_weights(self, n):
         """gSDE exploration matrices, one per env: [n, latent, act] ~ N(0, exp(log_std)^2)."""
@@ -97,14 +104,16 @@ class ActorCritic(nn.Module):
 class PPO:
     """Rollout + update over a ``UsvVectorEnv`` (any registered id with a Box action space)."""
 
-    def __init__(self, env, n_steps=32, batch_size=4096, seed=0, **cfg):
+    def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, **cfg):
         from gym_usv_amd.sb3 import DeviceFrameStack
         self.cfg = dict(CONFIG_PPO, **cfg)
         self.env, self.n_steps, self.batch_size = env, n_steps, batch_size
         self.device = env.device
         self.N, D, A = env.num_envs, env.obs_dim, env.act_dim
         self.D = D
-        self.stack = DeviceFrameStack(self.N, D, self.cfg["n_stack"], self.device)
+        self.fused = fused
+        if not fused:
+            self.stack = DeviceFrameStack(self.N, D, self.cfg["n_stack"], self.device)
         torch.manual_seed(seed)
         self.model = ActorCritic(D * self.cfg["n_stack"], A, self.cfg["hidden"], self.cfg["log_std_init"],
                                  self.cfg["use_sde"]).to(self.device)
@@ -113,6 +122,20 @@ class PPO:
         self.a_lo = torch.as_tensor(lo, device=self.device, dtype=torch.float32)
         self.a_hi = torch.as_tensor(hi, device=self.device, dtype=torch.float32)
         obs, _ = env.reset(seed=seed)
+        self.abs_ye = []                                # mean |ye| (m) of every step's obs
+        self.env_steps = 0
+        self.W = None
+        if fused:
+            from gym_usv_amd.rollout import DeviceRollout
+            from gym_usv_amd.wrappers import DeviceWrappers
+            k = self.cfg["n_stack"]
+            self.wr = DeviceWrappers(self.N, D, k, self.device, env.reward.dtype)
+            self.ro = DeviceRollout(self.N, n_steps, k * D, A, self.device, env.reward.dtype)
+            self.wr.reset(obs)
+            # the update reads the rollout's own buffers
+            self.b_obs, self.b_act, self.b_logp, self.b_val = self.ro.obs, self.ro.act, self.ro.logp, self.ro.val
+            self._totals = (0.0, 0, 0)
+            return
         self.obs = self.stack.reset(obs).clone()
         T, N = n_steps, self.N
         z = lambda *s: torch.zeros(s, device=self.device)   # noqa: E731
@@ -121,12 +144,33 @@ class PPO:
         self.b_rew, self.b_done = z(T, N), z(T, N)
         self.ep_ret, self.ep_len = z(N), z(N)
         self.finished = []                              # (return, length) of completed episodes
-        self.abs_ye = []                                # mean |ye| (m) of every step's obs
-        self.env_steps = 0
-        self.W = None
+
+    @torch.no_grad()
+    def rollout_fused(self):
+        """The rollout on DeviceWrappers + DeviceRollout: nothing here waits for the device."""
+        sde, freq = self.cfg["use_sde"], self.cfg["sde_sample_freq"]
+        wr, ro = self.wr, self.ro
+        for t in range(self.n_steps):
+            if sde and (t == 0 or (freq > 0 and t % freq == 0)):   # reset_noise (SB3 collect_rollouts)
+                self.W = self.model.sample_weights(self.N)
+            obs = wr.stacked                                        # the ring's window, no clone
+            dist, lat = self.model.dist(obs, validate=False)
+            if sde:
+                a = dist.mean + torch.bmm(lat.unsqueeze(1), self.W).squeeze(1)
+            else:
+                a = dist.sample()
+            ro.put_obs(t, obs, a.contiguous(), self.model.value(obs), dist.log_prob(a).sum(-1))
+            a_env = torch.max(torch.min(a, self.a_hi), self.a_lo)          # SB3 clips Box actions
+            o, rew, term, trunc, info = self.env.step(a_env)
+            self.abs_ye.append(o[:, 5].abs().mean() * 10.0)   # obs[5] = ye / 10 (simple_env.py:79-80)
+            _, final_stack, _ = wr.step(o, rew, info["_final_obs"], info["final_obs"])
+            ro.put_step(t, rew, term, trunc, final_stack)
+            self.env_steps += self.N
 
     @torch.no_grad()
     def rollout(self):
+        if self.fused:
+            return self.rollout_fused()
         g, sde, freq = self.cfg["gamma"], self.cfg["use_sde"], self.cfg["sde_sample_freq"]
         for t in range(self.n_steps):
             if sde and (t == 0 or (freq > 0 and t % freq == 0)):   # reset_noise (SB3 collect_rollouts)
@@ -167,6 +211,9 @@ class PPO:
 
     def advantages(self):
         g, lam = self.cfg["gamma"], self.cfg["gae_lambda"]
+        if self.fused:
+            with torch.no_grad():                       # one forward pass over the terminal rows
+                return self.ro.gae(self.model.value(self.wr.stacked), self.model.value(self.ro.term_obs), g, lam)
         with torch.no_grad():
             last_v = self.model.value(self.obs)
         adv = torch.zeros_like(self.b_rew)
@@ -212,6 +259,14 @@ class PPO:
     def episode_stats(self):
         out = {"mean_abs_ye": float(torch.stack(self.abs_ye).mean())} if self.abs_ye else {}
         self.abs_ye = []
+        if self.fused:                                  # DeviceWrappers' cumulative counters, once per update
+            now, was = self.wr.totals(), self._totals
+            self._totals = now
+            eps = now[1] - was[1]
+            if eps == 0:
+                return {"episodes": 0, **out}
+            return {"episodes": eps, "ep_rew_mean": (now[0] - was[0]) / eps, "ep_len_mean": (now[2] - was[2]) / eps,
+                    **out}
         if not self.finished:
             return {"episodes": 0, **out}
         f = torch.cat(self.finished)
@@ -220,10 +275,11 @@ class PPO:
                 "ep_len_mean": float(f[:, 1].mean()), **out}
 
 
-def train(env_id="usv-simple", envs=4096, updates=10, n_steps=32, batch_size=4096, seed=0, log=print, **cfg):
+def train(env_id="usv-simple", envs=4096, updates=10, n_steps=32, batch_size=4096, seed=0, log=print, fused=False,
+          **cfg):
     import gym_usv_amd
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False)   # each step is consumed at once
-    ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, **cfg)
+    ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, **cfg)
     hist = []
     t0 = time.perf_counter()
     for u in range(updates):
@@ -246,6 +302,7 @@ def main():
     ap.add_argument("--batch-size", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-sde", action="store_true", help="state-independent log-std instead of gSDE")
+    ap.add_argument("--fused", action="store_true", help="DeviceWrappers + DeviceRollout: a sync-free rollout")
     ap.add_argument("--log", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     f = open(a.log, "a") if a.log else None
@@ -257,8 +314,10 @@ def main():
             f.flush()
     if f:
         log(json.dumps({"config": {**CONFIG_PPO, "use_sde": not a.no_sde, "env_id": a.env_id, "envs": a.envs,
-                                   "n_steps": a.n_steps, "batch_size": a.batch_size, "seed": a.seed}}))
-    train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, use_sde=not a.no_sde)
+                                   "n_steps": a.n_steps, "batch_size": a.batch_size, "seed": a.seed,
+                                   "fused": a.fused}}))
+    train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, fused=a.fused,
+          use_sde=not a.no_sde)
 
 
 if __name__ == "__main__":

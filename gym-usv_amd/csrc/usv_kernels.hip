@@ -18,6 +18,8 @@
 //   usv_wrap.hpp          frame stack + episode statistics behind the step (usv_wrap_step / _reset)
 //   usv_norm_math.hpp     VecNormalize: moments arithmetic, work split, transform (host C++, no HIP)
 //   usv_norm.hpp          VecNormalize in front of the frame stack (usv_wrap_step_norm / _reset_norm)
+//   usv_rollout_math.hpp  rollout buffer: bootstrap, GAE step, terminal-slot numbering (host C++, no HIP)
+//   usv_rollout.hpp       RolloutBuffer + truncation bootstrap + GAE (usv_rollout_put_obs / _put_step / _gae)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -43,6 +45,7 @@
 #include "usv_noscan_step.hpp"   // (after the others: the kernels before it keep their place in the code object)
 #include "usv_wrap.hpp"
 #include "usv_norm.hpp"
+#include "usv_rollout.hpp"
 
 
 // ============================================================================= host side
@@ -1046,6 +1049,118 @@ int usv_wrap_step_norm(const usv_wrap* w, const usv_norm* zn, int64_t j, const f
     if (no) hipLaunchKernelGGL((wrap_step_norm_kernel<float, true>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
     else hipLaunchKernelGGL((wrap_step_norm_kernel<float, false>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
   }
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- device rollout buffer (usv_rollout.hpp)
+size_t usv_rollout_scratch_bytes(int32_t n) {
+  return n > 0 ? 2 * sizeof(long long) + (((size_t)ro_num_chunks(n) * sizeof(int32_t) + 7) & ~(size_t)7) : 0;
+}
+
+// The checks that need no HIP call (`more`: the call's own buffers, all 4-B aligned or coarser), then the
+// device of every buffer; fills the kernels' arguments.
+static int rollout_args(const usv_rollout* ro, bool in_range, std::initializer_list<const void*> more, RoArgs& a,
+                        int& dev) {
+  if (!ro) return fail(USV_ERR_ARG, "null usv_rollout");
+  if (ro->n <= 0 || ro->n_steps <= 0 || ro->obs_width <= 0 || ro->act_dim <= 0)
+    return fail(USV_ERR_ARG, "usv_rollout: n, n_steps, obs_width and act_dim must be > 0");
+  if (ro->term_cap < 0 || ro->reserved != 0) return fail(USV_ERR_ARG, "usv_rollout: term_cap must be >= 0 and reserved 0");
+  if (!in_range) return fail(USV_ERR_ARG, "usv_rollout: t must be in [0, n_steps)");
+  const void* const own[] = {ro->obs, ro->act, ro->rew, ro->val, ro->logp, ro->adv, ro->ret, ro->start,
+                             ro->term_slot, ro->term_count, ro->scratch, ro->term_cap > 0 ? ro->term_obs : ro->obs};
+  for (const void* p : own)
+    if (!p) return fail(USV_ERR_ARG, "usv_rollout: null buffer");
+  for (const void* p : more)
+    if (!p) return fail(USV_ERR_ARG, "usv_rollout: null argument");
+  auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
+  for (const void* p : own)
+    if (p != (const void*)ro->start && misaligned(p, p == ro->scratch ? 8 : 4))
+      return fail(USV_ERR_ARG, "usv_rollout: a buffer is not aligned to its element size");
+  auto device_of = [](const void* p) {
+    hipPointerAttribute_t pa{};
+    return hipPointerGetAttributes(&pa, p) == hipSuccess ? pa.device : -1;
+  };
+  dev = device_of(ro->obs);
+  if (dev < 0) { (void)hipGetLastError(); return fail(USV_ERR_ARG, "usv_rollout: obs is not a device pointer"); }
+  bool same = true;
+  for (const void* p : own) same = same && device_of(p) == dev;
+  for (const void* p : more) same = same && device_of(p) == dev;
+  if (!same) {
+    (void)hipGetLastError();
+    return fail(USV_ERR_ARG, "usv_rollout: a buffer is not a device pointer on the device that holds obs");
+  }
+  long long* const totals = (long long*)ro->scratch;
+  a = RoArgs{ro->n, ro->n_steps, ro->obs_width, ro->act_dim, ro->term_cap, ro->obs, ro->act, ro->rew, ro->val,
+             ro->logp, ro->adv, ro->ret, ro->start, ro->term_slot, ro->term_obs, ro->term_count, totals,
+             (int32_t*)(totals + 2)};
+  return USV_OK;
+}
+
+// USV_ROLLOUT_STORE=wt | plain overrides the obs store's policy (tools/rollout_ab.py measures both).
+static bool rollout_store_wt() {
+  const char* const s = std::getenv("USV_ROLLOUT_STORE");
+  return s ? std::strcmp(s, "wt") == 0 : kRolloutStoreWt;
+}
+
+int usv_rollout_put_obs(const usv_rollout* ro, int32_t t, const float* obs_src, size_t stride, const float* act,
+                        const float* val, const float* logp, void* stream) {
+  RoArgs a;
+  int dev;
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+  if (ro && ro->obs_width > 0 && stride < (size_t)ro->obs_width)
+    return fail(USV_ERR_ARG, "usv_rollout_put_obs: the row stride is below obs_width");
+  if (misaligned(obs_src) || misaligned(act) || misaligned(val) || misaligned(logp))
+    return fail(USV_ERR_ARG, "usv_rollout_put_obs: a buffer is not 4-B aligned");
+  if (int rc = rollout_args(ro, ro && t >= 0 && t < ro->n_steps, {obs_src, act, val, logp}, a, dev)) return rc;
+  DeviceGuard g(dev);
+  const int per_block = kWaves * kWrapEnvs;
+  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
+  if (rollout_store_wt())
+    hipLaunchKernelGGL(rollout_obs_kernel<true>, grid, block, 0, (hipStream_t)stream, a, (int)t, obs_src, stride, act, val, logp);
+  else
+    hipLaunchKernelGGL(rollout_obs_kernel<false>, grid, block, 0, (hipStream_t)stream, a, (int)t, obs_src, stride, act, val, logp);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_rollout_put_step(const usv_rollout* ro, int32_t t, const void* rew, int32_t reward_bytes, const uint8_t* term,
+                         const uint8_t* trunc, const float* final_stack, void* stream) {
+  RoArgs a;
+  int dev;
+  if (reward_bytes != 4 && reward_bytes != 8) return fail(USV_ERR_ARG, "usv_rollout_put_step: reward_bytes must be 4 or 8");
+  if ((reinterpret_cast<uintptr_t>(rew) & (uintptr_t)(reward_bytes - 1)) != 0 || (reinterpret_cast<uintptr_t>(final_stack) & 3) != 0)
+    return fail(USV_ERR_ARG, "usv_rollout_put_step: a buffer is not aligned to its element size");
+  const bool need_fs = ro && ro->term_cap > 0;          // without slots no terminal row is ever read
+  if (int rc = rollout_args(ro, ro && t >= 0 && t < ro->n_steps,
+                            {rew, term, trunc, need_fs ? (const void*)final_stack : rew}, a, dev))
+    return rc;
+  DeviceGuard g(dev);
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(ro_num_chunks(a.n)), block(kBlock);
+  hipLaunchKernelGGL(rollout_count_kernel, grid, block, 0, s, a, term, trunc);
+  if (reward_bytes == 8)
+    hipLaunchKernelGGL(rollout_step_kernel<double>, grid, block, 0, s, a, (int)t, (const double*)rew, term, trunc, final_stack);
+  else
+    hipLaunchKernelGGL(rollout_step_kernel<float>, grid, block, 0, s, a, (int)t, (const float*)rew, term, trunc, final_stack);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_rollout_gae(const usv_rollout* ro, const float* last_val, const float* term_val, double gamma,
+                    double gae_lambda, void* stream) {
+  RoArgs a;
+  int dev;
+  if (!(gamma >= 0.0 && gamma <= 1.0) || !(gae_lambda >= 0.0 && gae_lambda <= 1.0))
+    return fail(USV_ERR_ARG, "usv_rollout_gae: gamma and gae_lambda must be in [0, 1]");
+  if ((reinterpret_cast<uintptr_t>(last_val) & 3) != 0 || (reinterpret_cast<uintptr_t>(term_val) & 3) != 0)
+    return fail(USV_ERR_ARG, "usv_rollout_gae: a buffer is not 4-B aligned");
+  if (ro && ro->term_cap > 0 && !term_val) return fail(USV_ERR_ARG, "usv_rollout_gae: term_val is missing while term_cap > 0");
+  if (int rc = rollout_args(ro, true, {last_val, term_val ? (const void*)term_val : last_val}, a, dev)) return rc;
+  DeviceGuard g(dev);
+  const dim3 grid((a.n + kBlock - 1) / kBlock), block(kBlock);
+  hipLaunchKernelGGL(rollout_gae_kernel, grid, block, 0, (hipStream_t)stream, a, last_val, term_val, ro_g32(gamma),
+                     ro_gl32(gamma, gae_lambda));
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

@@ -82,6 +82,16 @@ class UsvNorm(ctypes.Structure):
                 ("scratch", ctypes.c_void_p)]
 
 
+class UsvRollout(ctypes.Structure):
+    """usv_rollout: the caller-owned device buffers of the rollout buffer (usv_rollout_put_obs / _put_step / _gae)."""
+    _fields_ = [("n", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("obs_width", ctypes.c_int32),
+                ("act_dim", ctypes.c_int32), ("term_cap", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("obs", ctypes.c_void_p), ("act", ctypes.c_void_p), ("rew", ctypes.c_void_p),
+                ("val", ctypes.c_void_p), ("logp", ctypes.c_void_p), ("adv", ctypes.c_void_p),
+                ("ret", ctypes.c_void_p), ("start", ctypes.c_void_p), ("term_slot", ctypes.c_void_p),
+                ("term_obs", ctypes.c_void_p), ("term_count", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
+
+
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
 _i64 = ctypes.c_int64
@@ -122,6 +132,10 @@ SIGNATURES = [
     ("usv_wrap_step_norm", ctypes.c_int, [ctypes.POINTER(UsvWrap), ctypes.POINTER(UsvNorm), _i64, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp]),
     ("usv_wrap_reset_norm", ctypes.c_int, [ctypes.POINTER(UsvWrap), ctypes.POINTER(UsvNorm), _i64, _vp, _vp, _vp]),
+    ("usv_rollout_scratch_bytes", _sz, [_i32]),
+    ("usv_rollout_put_obs", ctypes.c_int, [ctypes.POINTER(UsvRollout), _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("usv_rollout_put_step", ctypes.c_int, [ctypes.POINTER(UsvRollout), _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    ("usv_rollout_gae", ctypes.c_int, [ctypes.POINTER(UsvRollout), _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
 ]
 
 _LIBS = {}

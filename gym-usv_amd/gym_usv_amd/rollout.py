@@ -1,0 +1,158 @@
+"""SB3's ``RolloutBuffer`` on the device, behind ``UsvVectorEnv.step`` and ``DeviceWrappers.step``.
+
+``DeviceRollout`` is ``RolloutBuffer.add`` and ``compute_returns_and_advantage``
+(stable_baselines3/common/buffers.py) plus the truncation bootstrap of
+``OnPolicyAlgorithm.collect_rollouts`` as HIP kernels (``usv_rollout_*``, include/usv_hip.h) on the
+current stream.  A rollout of T steps makes no host sync between its first action and its advantages::
+
+    wr = DeviceWrappers(env.num_envs, env.obs_dim, 5, env.device, env.reward.dtype)
+    ro = DeviceRollout(env.num_envs, T, 5 * env.obs_dim, env.act_dim, env.device, env.reward.dtype)
+    for t in range(T):
+        a, v, logp = policy(wr.stacked)                   # the ring's window, read in place
+        ro.put_obs(t, wr.stacked, a, v, logp)             # before the step: the next push overwrites it
+        obs, rew, term, trunc, info = env.step(clip(a))
+        _, final_stack, _ = wr.step(obs, rew, info["_final_obs"], info["final_obs"])
+        ro.put_step(t, rew, term, trunc, final_stack)
+    ro.gae(value(wr.stacked), value(ro.term_obs), gamma, gae_lambda)
+    ro.adv, ro.ret                                        # [T, N]
+
+All buffer arithmetic is float32 with every operation rounded on its own, as NumPy computes SB3's;
+tests/rollout_ref.py restates it and the kernels equal it bit for bit.  ``rew`` keeps the raw reward: the
+bootstrapped value enters inside ``gae`` only, so ``gae`` may be called again and gives the same bits.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+
+from . import _lib
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+class DeviceRollout:
+    """``n_steps`` steps of ``num_envs`` envs whose observations are ``obs_width`` floats (the stacked
+    width, ``k * D``) and whose actions are ``act_dim`` floats.
+
+    Buffers (torch tensors on ``device``): ``obs`` [T, N, W], ``act`` [T, N, A], ``rew`` / ``val`` /
+    ``logp`` / ``adv`` / ``ret`` [T, N] float32, ``start`` [T + 1, N] uint8 (SB3's ``episode_starts``;
+    row 0 starts as ones and ``gae`` carries row T into it for the next rollout), ``term_slot`` [T, N]
+    int32 and ``term_obs`` [term_cap, W].
+
+    An env that is truncated and not terminated (the adapter's ``TimeLimit.truncated``) bootstraps: its
+    terminal observation goes to ``term_obs[s]``, ``term_slot[t, e] = s``, and ``gae`` adds
+    ``gamma * term_val[s]`` to its reward.  Slots count such (t, env) pairs in order from 0 in every
+    rollout.  ``term_cap`` defaults to ``2 * num_envs``: envs that were reset together reach the
+    TimeLimit in the same step, so ``num_envs`` slots in one step is the normal case.  Overflow: a pair
+    whose number is not below ``term_cap`` gets ``term_slot = -1`` and **no bootstrap** (its episode end
+    is treated as a termination); ``counts()`` reports how many.
+
+    ``reward_dtype`` is the dtype ``put_step`` will be given (float32: an f32 env or
+    ``DeviceWrappers.norm_rew``; float64: an f64 env).  There is no CPU fallback."""
+
+    def __init__(self, num_envs, n_steps, obs_width, act_dim, device, reward_dtype=torch.float32, term_cap=None,
+                 lib_path=None):
+        n, T, W, A = int(num_envs), int(n_steps), int(obs_width), int(act_dim)
+        if n <= 0 or T <= 0 or W <= 0 or A <= 0:
+            raise ValueError("num_envs, n_steps, obs_width and act_dim must be > 0")
+        cap = 2 * n if term_cap is None else int(term_cap)
+        if cap < 0:
+            raise ValueError("term_cap must be >= 0")
+        if reward_dtype not in (torch.float32, torch.float64):
+            raise ValueError("reward_dtype must be torch.float32 or torch.float64")
+        device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+        if device.type != "cuda":
+            raise _lib.UsvLibError("DeviceRollout runs on a ROCm GPU only (no CPU fallback)")
+        self.lib = _lib.load(lib_path)
+        self.n, self.n_steps, self.w, self.a, self.term_cap = n, T, W, A, cap
+        self.device, self.reward_dtype = device, reward_dtype
+        f4 = dict(dtype=torch.float32, device=device)
+        self.obs = torch.zeros((T, n, W), **f4)
+        self.act = torch.zeros((T, n, A), **f4)
+        self.rew, self.val, self.logp, self.adv, self.ret = (torch.zeros((T, n), **f4) for _ in range(5))
+        self.start = torch.zeros((T + 1, n), dtype=torch.uint8, device=device)
+        self.start[0] = 1                               # _last_episode_starts = np.ones
+        self.term_slot = torch.full((T, n), -1, dtype=torch.int32, device=device)
+        self.term_obs = torch.zeros((max(cap, 1), W), **f4)[:cap]
+        self._count = torch.zeros(2, dtype=torch.int32, device=device)
+        self._scratch = torch.zeros(self.lib.usv_rollout_scratch_bytes(n) // 8, dtype=torch.int64, device=device)
+        self._bind()
+
+    def _bind(self):
+        """The C struct over the current buffers (again after a buffer was replaced)."""
+        self._ro = _lib.UsvRollout(self.n, self.n_steps, self.w, self.a, self.term_cap, 0, *(t.data_ptr() for t in (
+            self.obs, self.act, self.rew, self.val, self.logp, self.adv, self.ret, self.start, self.term_slot,
+            self.term_obs, self._count, self._scratch)))
+        self._rp = ctypes.byref(self._ro)
+
+    def _check(self, name, t, dtype, shape):
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+
+    def _check_t(self, t):
+        if not 0 <= int(t) < self.n_steps:
+            raise ValueError(f"t must be in [0, {self.n_steps})")
+        return int(t)
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def put_obs(self, t, obs, act, val, logp):
+        """Row ``t`` of ``obs`` / ``act`` / ``val`` / ``logp``: the observation the action was computed
+        from, the unclipped action, V(obs) and the log-probability.  ``obs`` is [N, W] with inner stride 1
+        and any row stride >= W (``DeviceWrappers.stacked`` is read in place); call it before the env
+        step, whose wrapper push overwrites that window's oldest frame."""
+        t = self._check_t(t)
+        n, W = self.n, self.w
+        if (obs.dtype != torch.float32 or tuple(obs.shape) != (n, W) or obs.device != self.device or
+                (W > 1 and obs.stride(1) != 1) or (n > 1 and obs.stride(0) < W)):
+            raise ValueError(f"obs must be a float32 tensor of shape {(n, W)} on {self.device} with inner stride 1 "
+                             f"and a row stride >= {W}")
+        self._check("act", act, torch.float32, (n, self.a))
+        self._check("val", val, torch.float32, (n,))
+        self._check("logp", logp, torch.float32, (n,))
+        stride = obs.stride(0) if n > 1 else W
+        _lib.check(self.lib.usv_rollout_put_obs(self._rp, t, _ptr(obs), stride, _ptr(act), _ptr(val), _ptr(logp),
+                                                self._stream()), self.lib)
+
+    def put_step(self, t, rew, term, trunc, final_stack):
+        """``rew[t]``, ``start[t + 1] = term | trunc`` and the terminal rows of the envs that bootstrap,
+        taken from ``final_stack`` [N, W] (``DeviceWrappers.step``'s, or ``info["final_obs"]`` without a
+        stack; only rows of done envs are read)."""
+        t = self._check_t(t)
+        n = self.n
+        self._check("rew", rew, self.reward_dtype, (n,))
+        for name, m in (("term", term), ("trunc", trunc)):
+            if m.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"{name} must be a bool or uint8 tensor")
+            self._check(name, m, m.dtype, (n,))
+        if final_stack is not None or self.term_cap > 0:
+            if final_stack is None:
+                raise ValueError("final_stack is needed while term_cap > 0")
+            self._check("final_stack", final_stack, torch.float32, (n, self.w))
+        _lib.check(self.lib.usv_rollout_put_step(self._rp, t, _ptr(rew), 4 if self.reward_dtype == torch.float32 else 8,
+                                                 _ptr(term), _ptr(trunc), _ptr(final_stack), self._stream()), self.lib)
+
+    def gae(self, last_val, term_val, gamma, gae_lambda):
+        """``compute_returns_and_advantage`` into ``adv`` / ``ret`` with ``last_val`` [N] = V of the
+        observation after the last step and ``term_val`` [term_cap] = V(``term_obs``) (read only at the
+        slots in use; None with ``term_cap == 0``).  Returns ``(adv, ret)``."""
+        self._check("last_val", last_val, torch.float32, (self.n,))
+        if term_val is not None or self.term_cap > 0:
+            if term_val is None:
+                raise ValueError("term_val is needed while term_cap > 0")
+            self._check("term_val", term_val, torch.float32, (self.term_cap,))
+        if not (0 <= float(gamma) <= 1 and 0 <= float(gae_lambda) <= 1):
+            raise ValueError("gamma and gae_lambda must be in [0, 1]")
+        _lib.check(self.lib.usv_rollout_gae(self._rp, _ptr(last_val), _ptr(term_val), float(gamma), float(gae_lambda),
+                                            self._stream()), self.lib)
+        return self.adv, self.ret
+
+    def counts(self):
+        """(terminal rows stored, pairs dropped for lack of a slot) of the current rollout as Python
+        ints: one host copy, the only sync of this class."""
+        c = self._count.tolist()
+        return int(c[0]), int(c[1])

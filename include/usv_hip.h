@@ -394,6 +394,79 @@ int usv_wrap_step_norm(const usv_wrap* w, const usv_norm* z, int64_t j, const fl
 int usv_wrap_reset_norm(const usv_wrap* w, const usv_norm* z, int64_t j, const uint8_t* mask_dev,
                         const float* obs_dev, void* stream);
 
+/* Device rollout buffer: SB3's RolloutBuffer (stable_baselines3/common/buffers.py) and the truncation
+ * bootstrap of OnPolicyAlgorithm.collect_rollouts (common/on_policy_algorithm.py) behind usv_step and
+ * usv_wrap_step on the same stream, with no host sync between a rollout's first action and its advantages.
+ * Additive, handle-free and stream-ordered like usv_wrap_* (ABI v5 addition); launched on the device that
+ * holds `obs`.  All buffer arithmetic is float32, every operation rounded on its own (no FMA), as NumPy
+ * computes it; tests/rollout_ref.py restates it and the kernels equal it bit for bit.
+ *
+ * A rollout is n_steps = T steps of n envs whose stored observation rows are obs_width = W floats.
+ *
+ * usv_rollout_put_obs(ro, t, ...), before the env step t (the wrappers' next push overwrites the oldest
+ * frame of the window it reads):                            <- RolloutBuffer.add
+ *   obs[t] = obs_src rows (any 4-B-aligned base, row stride >= W floats: DeviceWrappers.stacked, the
+ *            ring's window with row stride usv_wrap_ring_stride, is read in place, without a clone);
+ *   act[t] = act_dev [n][act_dim] (the unclipped action), val[t] = val_dev [n], logp[t] = logp_dev [n].
+ * usv_rollout_put_step(ro, t, ...), after the env step t:
+ *   rew[t] = float32(reward) (read as f32 or f64 by reward_bytes)   <- add: self.rewards[pos] = reward
+ *   start[t + 1] = terminated | truncated                           <- collect_rollouts:
+ *                                                                      self._last_episode_starts = dones
+ *   an env with truncated and not terminated (the adapter's TimeLimit.truncated) takes a terminal slot s
+ *   and term_obs[s] = its row of final_stack_dev [n][W] (usv_wrap_step's final_stack, or the step's final
+ *   obs without a stack); term_slot[t][e] = s, and -1 for every other env
+ *                                                    <- collect_rollouts: infos[idx]["terminal_observation"]
+ *   Slots are deterministic: s is the number of such (t', e') pairs earlier in (t, env) order within the
+ *   rollout.  t == 0 restarts the numbering.  A pair whose number is >= term_cap gets -1 and no bootstrap;
+ *   term_count = (pairs stored, pairs dropped) after every call.  Calls of one rollout pass t = 0, 1, ...
+ * usv_rollout_gae(ro, last_val_dev [n], term_val_dev [term_cap], gamma, gae_lambda), after step T - 1, with
+ *   term_val[s] = the caller's V(term_obs[s]) and g32 = float32(gamma), gl32 = float32(gamma * gae_lambda):
+ *   for t = T - 1 .. 0, gae = 0 at the start:               <- compute_returns_and_advantage
+ *     r     = rew[t], or rew[t] + g32 * term_val[term_slot[t]] where the slot is >= 0
+ *                                                    <- collect_rollouts: rewards[idx] += gamma * terminal_value
+ *     nnt   = 1 - start[t + 1];  nv = val[t + 1], last_val at t = T - 1
+ *     delta = (r + ((g32 * nv) * nnt)) - val[t]
+ *     gae   = delta + ((gl32 * nnt) * gae)
+ *     adv[t] = gae;  ret[t] = adv[t] + val[t]
+ *   then start[0] = start[T]: row T of one rollout is row 0 of the next (the caller starts the first
+ *   rollout with start[0] = 1, SB3's _last_episode_starts = np.ones).  term_val is read only at slots that
+ *   term_slot references.
+ * Deviation from SB3: rew keeps the raw reward and the bootstrapped value lives inside the GAE only,
+ * where SB3 adds it into buffer.rewards (which PPO never reads again); calling usv_rollout_gae twice
+ * therefore gives the same bits.
+ *
+ * USV_ERR_ARG, before any HIP call, for a NULL usv_rollout, n / n_steps / obs_width / act_dim <= 0,
+ * term_cap < 0, reserved != 0, t outside [0, n_steps), reward_bytes not 4 / 8, a row stride below
+ * obs_width, gamma or gae_lambda outside [0, 1] (or NaN), a NULL buffer or one not aligned to its element
+ * size (scratch: 8 B); term_obs, final_stack_dev and term_val_dev may be NULL only with term_cap == 0.
+ * Then for a buffer that is not device memory of the device that holds obs.  scratch needs
+ * usv_rollout_scratch_bytes(n) bytes and belongs to the rollout between put_step(0) and the gae. */
+typedef struct usv_rollout {   /* caller-owned device buffers */
+  int32_t n, n_steps, obs_width, act_dim;
+  int32_t term_cap;            /* rows of term_obs */
+  int32_t reserved;            /* 0 */
+  float* obs;                  /* [T][n][W] */
+  float* act;                  /* [T][n][act_dim] */
+  float* rew;                  /* [T][n] */
+  float* val;                  /* [T][n] */
+  float* logp;                 /* [T][n] */
+  float* adv;                  /* [T][n], written by usv_rollout_gae */
+  float* ret;                  /* [T][n], written by usv_rollout_gae */
+  uint8_t* start;              /* [T + 1][n] episode_starts */
+  int32_t* term_slot;          /* [T][n] */
+  float* term_obs;             /* [term_cap][W] */
+  int32_t* term_count;         /* [2] (stored, overflow) */
+  void* scratch;               /* usv_rollout_scratch_bytes(n) */
+} usv_rollout;
+size_t usv_rollout_scratch_bytes(int32_t n);   /* host only; 0 if bad */
+int usv_rollout_put_obs(const usv_rollout* ro, int32_t t, const float* obs_src_dev, size_t obs_row_stride_floats,
+                        const float* act_dev, const float* val_dev, const float* logp_dev, void* stream);
+int usv_rollout_put_step(const usv_rollout* ro, int32_t t, const void* rew_dev, int32_t reward_bytes,
+                         const uint8_t* term_dev, const uint8_t* trunc_dev, const float* final_stack_dev,
+                         void* stream);
+int usv_rollout_gae(const usv_rollout* ro, const float* last_val_dev, const float* term_val_dev, double gamma,
+                    double gae_lambda, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
