@@ -25,6 +25,10 @@ this image, so this is a compact PPO with the same hyper-parameters where they c
   window in place, the terminal observations are valued in one batch after the rollout, and a rollout
   makes no host sync: no ``.any()``, ``.nonzero()`` or ``bool()`` on a device tensor.  The buffer
   arithmetic is then SB3's float32 RolloutBuffer bit for bit; the default path is unchanged.
+* ``--frames`` (with ``--fused``; ``train(fused=True, frames=True)``): the rollout keeps one 143-float
+  frame per step and env instead of the 715-float stack (``DeviceRollout(n_stack=5)``) and the update
+  reads each minibatch through ``DeviceRollout.gather``, one launch that rebuilds the stacked rows and
+  fetches the five other fields.  The minibatches hold the same bits as without the flag.
 
 Rollout size at 4096 envs.  config_ppo's ``n_steps=2048, batch_size=64`` are for the reference's 4
 envs: 8 192 samples per update in 128 minibatches.  With 4096 envs the same n_steps would put 8.4 M
@@ -104,7 +108,7 @@ class ActorCritic(nn.Module):
 class PPO:
     """Rollout + update over a ``UsvVectorEnv`` (any registered id with a Box action space)."""
 
-    def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, **cfg):
+    def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, frames=False, **cfg):
         from gym_usv_amd.sb3 import DeviceFrameStack
         self.cfg = dict(CONFIG_PPO, **cfg)
         self.env, self.n_steps, self.batch_size = env, n_steps, batch_size
@@ -112,6 +116,9 @@ class PPO:
         self.N, D, A = env.num_envs, env.obs_dim, env.act_dim
         self.D = D
         self.fused = fused
+        if frames and not fused:
+            raise ValueError("frames=True needs fused=True")
+        self.frames = frames
         if not fused:
             self.stack = DeviceFrameStack(self.N, D, self.cfg["n_stack"], self.device)
         torch.manual_seed(seed)
@@ -130,7 +137,8 @@ class PPO:
             from gym_usv_amd.wrappers import DeviceWrappers
             k = self.cfg["n_stack"]
             self.wr = DeviceWrappers(self.N, D, k, self.device, env.reward.dtype)
-            self.ro = DeviceRollout(self.N, n_steps, k * D, A, self.device, env.reward.dtype)
+            self.ro = DeviceRollout(self.N, n_steps, k * D, A, self.device, env.reward.dtype,
+                                    n_stack=k if frames else None)
             self.wr.reset(obs)
             # the update reads the rollout's own buffers
             self.b_obs, self.b_act, self.b_logp, self.b_val = self.ro.obs, self.ro.act, self.ro.logp, self.ro.val
@@ -230,6 +238,8 @@ class PPO:
         c = self.cfg
         adv, ret = self.advantages()
         M = self.n_steps * self.N
+        if self.frames:
+            return self.update_frames(M)
         obs = self.b_obs.reshape(M, -1)
         act = self.b_act.reshape(M, -1)
         logp0, adv, ret = self.b_logp.reshape(M), adv.reshape(M), ret.reshape(M)
@@ -245,6 +255,33 @@ class PPO:
                 ratio = (logp - logp0[i]).exp()
                 pg = -torch.min(ratio * a_, ratio.clamp(1 - c["clip"], 1 + c["clip"]) * a_).mean()
                 vl = ((self.model.value(obs[i]) - ret[i]) ** 2).mean()
+                ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
+                loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
+                self.opt.zero_grad(set_to_none=True)
+                loss.backward()
+                nn.utils.clip_grad_norm_(self.model.parameters(), c["max_grad_norm"])
+                self.opt.step()
+                stats.append(torch.stack((pg.detach(), vl.detach(), ent.detach())))
+        s = torch.stack(stats).mean(0).tolist()
+        return {"policy_loss": s[0], "value_loss": s[1], "entropy": s[2],
+                "std_mean": float(self.model.log_std.detach().exp().mean())}
+
+    def update_frames(self, M):
+        """``update``'s loop with every minibatch read by ``DeviceRollout.gather`` (frame storage has no
+        ``[T * N, W]`` view to index)."""
+        c = self.cfg
+        stats = []
+        for _ in range(c["n_epochs"]):
+            perm = torch.randperm(M, device=self.device)
+            for k in range(0, M, self.batch_size):
+                mb = self.ro.gather(perm[k:k + self.batch_size])
+                a_ = mb.advantages
+                a_ = (a_ - a_.mean()) / (a_.std() + 1e-8)
+                dist, _ = self.model.dist(mb.observations)
+                logp = dist.log_prob(mb.actions).sum(-1)
+                ratio = (logp - mb.old_log_prob).exp()
+                pg = -torch.min(ratio * a_, ratio.clamp(1 - c["clip"], 1 + c["clip"]) * a_).mean()
+                vl = ((self.model.value(mb.observations) - mb.returns) ** 2).mean()
                 ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
                 loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
                 self.opt.zero_grad(set_to_none=True)
@@ -276,10 +313,10 @@ class PPO:
 
 
 def train(env_id="usv-simple", envs=4096, updates=10, n_steps=32, batch_size=4096, seed=0, log=print, fused=False,
-          **cfg):
+          frames=False, **cfg):
     import gym_usv_amd
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False)   # each step is consumed at once
-    ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, **cfg)
+    ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, frames=frames, **cfg)
     hist = []
     t0 = time.perf_counter()
     for u in range(updates):
@@ -303,8 +340,12 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-sde", action="store_true", help="state-independent log-std instead of gSDE")
     ap.add_argument("--fused", action="store_true", help="DeviceWrappers + DeviceRollout: a sync-free rollout")
+    ap.add_argument("--frames", action="store_true",
+                    help="with --fused: one frame per step in the rollout, minibatches by DeviceRollout.gather")
     ap.add_argument("--log", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
+    if a.frames and not a.fused:
+        ap.error("--frames needs --fused")
     f = open(a.log, "a") if a.log else None
 
     def log(s):
@@ -315,8 +356,8 @@ def main():
     if f:
         log(json.dumps({"config": {**CONFIG_PPO, "use_sde": not a.no_sde, "env_id": a.env_id, "envs": a.envs,
                                    "n_steps": a.n_steps, "batch_size": a.batch_size, "seed": a.seed,
-                                   "fused": a.fused}}))
-    train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, fused=a.fused,
+                                   "fused": a.fused, "frames": a.frames}}))
+    train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, fused=a.fused, frames=a.frames,
           use_sde=not a.no_sde)
 
 

@@ -20,6 +20,8 @@
 //   usv_norm.hpp          VecNormalize in front of the frame stack (usv_wrap_step_norm / _reset_norm)
 //   usv_rollout_math.hpp  rollout buffer: bootstrap, GAE step, terminal-slot numbering (host C++, no HIP)
 //   usv_rollout.hpp       RolloutBuffer + truncation bootstrap + GAE (usv_rollout_put_obs / _put_step / _gae)
+//   usv_rollout_frames_math.hpp  frame-deduplicated obs storage: rows, live mask, clear rule (host C++, no HIP)
+//   usv_rollout_frames.hpp  frame store and minibatch gather (usv_rollout_put_obs_frames / usv_rollout_gather)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -46,7 +48,7 @@
 #include "usv_wrap.hpp"
 #include "usv_norm.hpp"
 #include "usv_rollout.hpp"
-
+#include "usv_rollout_frames.hpp"
 
 // ============================================================================= host side
 using namespace usv;
@@ -1161,6 +1163,73 @@ int usv_rollout_gae(const usv_rollout* ro, const float* last_val, const float* t
   const dim3 grid((a.n + kBlock - 1) / kBlock), block(kBlock);
   hipLaunchKernelGGL(rollout_gae_kernel, grid, block, 0, (hipStream_t)stream, a, last_val, term_val, ro_g32(gamma),
                      ro_gl32(gamma, gae_lambda));
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- frame-deduplicated obs storage and the minibatch gather (usv_rollout_frames.hpp)
+// The checks of a usv_rollout_frames against its usv_rollout that need no HIP call.
+static int rollout_frames_check(const usv_rollout* ro, const usv_rollout_frames* fr) {
+  if (!ro) return fail(USV_ERR_ARG, "null usv_rollout");
+  if (!fr) return fail(USV_ERR_ARG, "null usv_rollout_frames");
+  if (fr->k < 1 || fr->d < 1) return fail(USV_ERR_ARG, "usv_rollout_frames: k and d must be >= 1");
+  if (fr->k > kRfMaxStack) return fail(USV_ERR_ARG, "usv_rollout_frames: k must be <= 32");
+  if ((int64_t)fr->k * fr->d != (int64_t)ro->obs_width)
+    return fail(USV_ERR_ARG, "usv_rollout_frames: k * d must equal obs_width");
+  if ((fr->flags & ~USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN) != 0) return fail(USV_ERR_ARG, "usv_rollout_frames: unknown flags");
+  if (((reinterpret_cast<uintptr_t>(fr->frames) | reinterpret_cast<uintptr_t>(fr->bad_count)) & 3) != 0)
+    return fail(USV_ERR_ARG, "usv_rollout_frames: a buffer is not 4-B aligned");
+  return USV_OK;
+}
+
+int usv_rollout_put_obs_frames(const usv_rollout* ro, const usv_rollout_frames* fr, int32_t t, const float* obs_src,
+                               size_t stride, const float* act, const float* val, const float* logp, void* stream) {
+  RoArgs a;
+  int dev;
+  if (int rc = rollout_frames_check(ro, fr)) return rc;
+  if (!fr->frames) return fail(USV_ERR_ARG, "usv_rollout_put_obs_frames: the rollout has no frames");
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+  if (ro->obs_width > 0 && stride < (size_t)ro->obs_width)
+    return fail(USV_ERR_ARG, "usv_rollout_put_obs_frames: the row stride is below obs_width");
+  if (misaligned(obs_src) || misaligned(act) || misaligned(val) || misaligned(logp))
+    return fail(USV_ERR_ARG, "usv_rollout_put_obs_frames: a buffer is not 4-B aligned");
+  usv_rollout r = *ro;
+  r.obs = fr->frames;                                   // frame mode has no obs; the frames name the device
+  if (int rc = rollout_args(&r, t >= 0 && t < ro->n_steps, {obs_src, act, val, logp}, a, dev)) return rc;
+  DeviceGuard g(dev);
+  const RfArgs f{fr->k, fr->d, fr->flags & USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN, fr->frames, fr->bad_count};
+  const int per_block = kWaves * kWrapEnvs;
+  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
+  hipLaunchKernelGGL(rollout_frames_obs_kernel, grid, block, 0, (hipStream_t)stream, a, f, (int)t, obs_src, stride, act,
+                     val, logp);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, const int64_t* idx, int32_t B,
+                       float* obs_out, float* act_out, float* val_out, float* logp_out, float* adv_out, float* ret_out,
+                       void* stream) {
+  RoArgs a;
+  int dev;
+  if (int rc = rollout_frames_check(ro, fr)) return rc;
+  if (B <= 0) return fail(USV_ERR_ARG, "usv_rollout_gather: B must be > 0");
+  if (!fr->bad_count) return fail(USV_ERR_ARG, "usv_rollout_gather: null bad_count");
+  if (!idx) return fail(USV_ERR_ARG, "usv_rollout_gather: null idx");
+  if (!obs_out || !act_out || !val_out || !logp_out || !adv_out || !ret_out)
+    return fail(USV_ERR_ARG, "usv_rollout_gather: null output");
+  if ((reinterpret_cast<uintptr_t>(idx) & 7) != 0) return fail(USV_ERR_ARG, "usv_rollout_gather: idx is not 8-B aligned");
+  for (const void* p : {obs_out, act_out, val_out, logp_out, adv_out, ret_out})
+    if ((reinterpret_cast<uintptr_t>(p) & 3) != 0) return fail(USV_ERR_ARG, "usv_rollout_gather: an output is not 4-B aligned");
+  usv_rollout r = *ro;
+  if (fr->frames) r.obs = fr->frames;
+  if (int rc = rollout_args(&r, true, {idx, fr->bad_count, obs_out, act_out, val_out, logp_out, adv_out, ret_out}, a, dev))
+    return rc;
+  DeviceGuard g(dev);
+  const RfArgs f{fr->k, fr->d, fr->flags & USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN, fr->frames, fr->bad_count};
+  const int per_block = kWaves * kRfRows;
+  const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
+  hipLaunchKernelGGL(rollout_gather_kernel, grid, block, 0, (hipStream_t)stream, a, f, idx, (int)B, obs_out, act_out,
+                     val_out, logp_out, adv_out, ret_out);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

@@ -1,0 +1,197 @@
+// usv_rollout_frames.hpp -- frame-deduplicated obs storage for the device rollout buffer and the
+// minibatch gather (SB3's RolloutBuffer.get / _get_samples): usv_rollout_put_obs_frames and
+// usv_rollout_gather (include/usv_hip.h).  The layout, the live mask and the clear rule are
+// usv_rollout_frames_math.hpp's.
+//
+//   rollout_frames_obs_kernel  rollout_obs_kernel (usv_rollout.hpp) with a destination row stride: row t
+//                              of act / val / logp, and of each env's window the columns that are new --
+//                              all k D at t = 0 (frame rows 0 .. k - 1), the newest D afterwards (frame
+//                              row t + k - 1).  A wave owns kWrapEnvs = 16 envs; a row is cut into 16-B
+//                              pieces at declared 4-B alignment, the last piece moved back to end with
+//                              the row, three pieces per lane in flight, plain stores.
+//   rollout_gather_kernel      a wave owns kRfRows = 4 consecutive samples.  Lane r < 4 reads idx[b0 + r],
+//                              checks it, splits it into (t, e), builds the live mask from at most k - 1
+//                              start bytes and moves the four scalars; the offsets and masks are then
+//                              broadcast (readlane: wave-uniform).  The obs rows are cut into 16-B pieces
+//                              as above, on both sides; lane l takes pieces l, l + 64, .. of all four rows,
+//                              so four loads are in flight per lane and the slot of each of a piece's four
+//                              columns is worked out once for the four rows.  The mask is applied per
+//                              element (a piece straddles frames when D is no multiple of 4) and only to
+//                              rows that have a cleared slot.  Without frames (full storage) the source
+//                              row is idx * W of obs and every slot is live.
+//                              An index outside [0, T n) is never used as an address: its obs row, action
+//                              and scalars are NaN and it is counted in bad_count (the kernel's only
+//                              atomic, an integer add: the outputs are bitwise reproducible).
+#pragma once
+
+#include "usv_rollout_frames_math.hpp"
+#include "usv_rollout.hpp"
+
+namespace usv {
+
+struct RfArgs {
+  int k, D, keep_sign;
+  float* frames;                // [n][T + k - 1][D], or null: full storage (gather only)
+  int32_t* bad;                 // [1]
+};
+
+__global__ __launch_bounds__(kBlock) void rollout_frames_obs_kernel(RoArgs a, RfArgs f, int t, const float* src,
+                                                                   size_t sstride, const float* act, const float* val,
+                                                                   const float* logp) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int l = lane_id();
+  const int e0 = (blockIdx.x * kWaves + wave) * kWrapEnvs;
+  const int ne = min(kWrapEnvs, a.n - e0);
+  if (ne <= 0) return;
+  const size_t row0 = (size_t)t * a.n + e0;             // first of the wave's rows in a [T][n] buffer
+  if (l < ne) {
+    a.val[row0 + l] = val[e0 + l];
+    a.logp[row0 + l] = logp[e0 + l];
+  }
+  for (int q = l; q < ne * a.A; q += kWave) a.act[row0 * a.A + q] = act[(size_t)e0 * a.A + q];
+  const int W = rf_put_width(t, f.k, f.D);              // the columns of the window that are new
+  const size_t dstride = (size_t)rf_rows(a.T, f.k) * f.D;
+  const float* const span = src + (size_t)e0 * sstride + rf_put_col(t, f.k, f.D);
+  float* const dst = f.frames + rf_row_offset(e0, rf_put_row(t, f.k), a.T, f.k, f.D);
+  if (W >= 4) {
+    const int P = (W + 3) / 4, np = ne * P;             // pieces per row, of the wave
+    const int dk = kWave / P, dr = kWave % P;
+    int k = l / P, r = l - k * P;                       // piece l + 64 i: row k, piece r of it
+    for (int q = l; q < np; q += 3 * kWave) {
+      const float* sp[3];
+      float* dp[3];
+      WrapQuad4 v[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const int c = min(4 * r, W - 4);
+        sp[i] = span + (size_t)k * sstride + c;
+        dp[i] = dst + (size_t)k * dstride + c;
+        k += dk;
+        r += dr;
+        if (r >= P) { r -= P; ++k; }
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if (q + i * kWave < np) v[i] = *reinterpret_cast<const WrapQuad*>(sp[i]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        if (q + i * kWave < np) *reinterpret_cast<WrapQuad*>(dp[i]) = v[i];
+    }
+  } else {
+    for (int q = l; q < ne * W; q += kWave) {
+      const int k = q / W, c = q - k * W;
+      dst[(size_t)k * dstride + c] = span[(size_t)k * sstride + c];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void rollout_gather_kernel(RoArgs a, RfArgs f, const int64_t* idx, int B,
+                                                               float* obs_out, float* act_out, float* val_out,
+                                                               float* logp_out, float* adv_out, float* ret_out) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int l = lane_id();
+  const int64_t b0 = ((int64_t)blockIdx.x * kWaves + wave) * kRfRows;
+  if (b0 >= B) return;
+  const int nb = (int)min((int64_t)kRfRows, B - b0);    // wave-uniform
+  const int64_t total = (int64_t)a.T * a.n;
+  const int W = a.W, D = f.D;
+  const float nan = __builtin_nanf("");
+  const bool keep = f.keep_sign != 0;
+  const uint32_t all = rf_all_live(f.k);
+  // ---- lane r < nb: sample b0 + r
+  bool ok = false;
+  uint32_t live = all;
+  unsigned long long off = 0;
+  if (l < nb) {
+    const int64_t i = idx[b0 + l];
+    ok = rf_index_ok(i, total);
+    float v = nan, lp = nan, ad = nan, rt = nan;
+    if (ok) {
+      v = a.val[i];
+      lp = a.logp[i];
+      ad = a.adv[i];
+      rt = a.ret[i];
+      if (f.frames) {
+        int64_t t;
+        if (total <= 0xffffffffll) t = (int64_t)((uint32_t)i / (uint32_t)a.n);
+        else t = i / a.n;
+        const int64_t e = i - t * a.n;
+        live = rf_live_mask(a.start, a.n, e, (int32_t)t, f.k);
+        off = rf_sample_offset(e, t, a.T, f.k, D);
+      } else {
+        off = (unsigned long long)i * (unsigned long long)W;
+      }
+    }
+    val_out[b0 + l] = v;
+    logp_out[b0 + l] = lp;
+    adv_out[b0 + l] = ad;
+    ret_out[b0 + l] = rt;
+  }
+  const unsigned long long bad = ballot(l < nb && !ok);
+  if (bad != 0ull && l == 0) atomicAdd(f.bad, (int)__builtin_popcountll(bad));
+  // ---- actions
+  for (int q = l; q < nb * a.A; q += kWave) {
+    const int r = q / a.A, c = q - r * a.A;
+    const int64_t i = idx[b0 + r];
+    act_out[(size_t)(b0 + r) * a.A + c] = rf_index_ok(i, total) ? a.act[(size_t)i * a.A + c] : nan;
+  }
+  // ---- obs rows
+  const float* const src = f.frames ? f.frames : a.obs;
+  if (W >= 4) {
+    size_t roff[kRfRows];
+    uint32_t rlive[kRfRows];
+    bool rok[kRfRows];
+#pragma unroll
+    for (int r = 0; r < kRfRows; ++r) {                 // wave-uniform copies of lane r's values
+      const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)off, r);
+      const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(off >> 32), r);
+      rlive[r] = __builtin_amdgcn_readlane(live, r);
+      rok[r] = r < nb && __builtin_amdgcn_readlane((uint32_t)ok, r) != 0;
+      // a refused or absent row loads row 0 instead (always there) and drops it: the four loads stay
+      // unconditional, so nothing waits between them
+      roff[r] = rok[r] ? (size_t)(((unsigned long long)hi << 32) | lo) : 0;
+    }
+    const int P = (W + 3) / 4;
+    for (int p = l; p < P; p += kWave) {
+      const int c = min(4 * p, W - 4);
+      int sl[4];                                        // the slots of columns c .. c + 3
+      {
+        int j = c / D, rem = c - j * D;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+          sl[x] = j;
+          if (++rem == D) { rem = 0; ++j; }
+        }
+      }
+      WrapQuad4 v[kRfRows];
+#pragma unroll
+      for (int r = 0; r < kRfRows; ++r) v[r] = *reinterpret_cast<const WrapQuad*>(src + roff[r] + c);
+#pragma unroll
+      for (int r = 0; r < kRfRows; ++r) {
+        if (r >= nb) continue;
+        WrapQuad4 o = {nan, nan, nan, nan};
+        if (rok[r]) {
+          o = v[r];
+          if (rlive[r] != all) {
+#pragma unroll
+            for (int x = 0; x < 4; ++x) o[x] = rf_slot_value(o[x], rlive[r], sl[x], keep);
+          }
+        }
+        *reinterpret_cast<WrapQuad*>(obs_out + (size_t)(b0 + r) * W + c) = o;
+      }
+    }
+  } else {
+    // W < 4: nb W <= 12 elements, one per lane; every lane takes part in the shuffles
+    const int r = min(l / W, nb - 1), c = l - (l / W) * W;
+    const int okr = __shfl((int)ok, r);
+    const unsigned long long ro = __shfl(off, r);
+    const uint32_t lv = __shfl(live, r);
+    if (l < nb * W) {
+      float o = nan;
+      if (okr) o = rf_slot_value(src[(size_t)ro + c], lv, c / D, keep);
+      obs_out[(size_t)(b0 + r) * W + c] = o;
+    }
+  }
+}
+
+}  // namespace usv

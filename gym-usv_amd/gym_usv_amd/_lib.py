@@ -92,6 +92,16 @@ class UsvRollout(ctypes.Structure):
                 ("term_obs", ctypes.c_void_p), ("term_count", ctypes.c_void_p), ("scratch", ctypes.c_void_p)]
 
 
+ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN = 1
+
+
+class UsvRolloutFrames(ctypes.Structure):
+    """usv_rollout_frames: the frame-deduplicated obs storage of a rollout and the gather's counter
+    (usv_rollout_put_obs_frames / usv_rollout_gather)."""
+    _fields_ = [("k", ctypes.c_int32), ("d", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("frames", ctypes.c_void_p), ("bad_count", ctypes.c_void_p)]
+
+
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
 _i64 = ctypes.c_int64
@@ -136,6 +146,10 @@ SIGNATURES = [
     ("usv_rollout_put_obs", ctypes.c_int, [ctypes.POINTER(UsvRollout), _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
     ("usv_rollout_put_step", ctypes.c_int, [ctypes.POINTER(UsvRollout), _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     ("usv_rollout_gae", ctypes.c_int, [ctypes.POINTER(UsvRollout), _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
+    ("usv_rollout_put_obs_frames", ctypes.c_int, [ctypes.POINTER(UsvRollout), ctypes.POINTER(UsvRolloutFrames), _i32,
+                                                  _vp, _sz, _vp, _vp, _vp, _vp]),
+    ("usv_rollout_gather", ctypes.c_int, [ctypes.POINTER(UsvRollout), ctypes.POINTER(UsvRolloutFrames), _vp, _i32, _vp,
+                                          _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _LIBS = {}

@@ -19,9 +19,20 @@ current stream.  A rollout of T steps makes no host sync between its first actio
 All buffer arithmetic is float32 with every operation rounded on its own, as NumPy computes SB3's;
 tests/rollout_ref.py restates it and the kernels equal it bit for bit.  ``rew`` keeps the raw reward: the
 bootstrapped value enters inside ``gae`` only, so ``gae`` may be called again and gives the same bits.
+
+The other half of ``RolloutBuffer``, ``get``, is one more kernel (``usv_rollout_gather``)::
+
+    for mb in ro.get(batch_size):                         # one device randperm, consecutive slices
+        mb.observations, mb.actions, mb.old_values, mb.old_log_prob, mb.advantages, mb.returns
+    mb = ro.gather(idx)                                   # any int64 [B] of flat indices t * N + e
+
+``DeviceRollout(..., n_stack=k)`` keeps one ``D``-float frame per (step, env) in ``frames``
+[N, T + k - 1, D] where the default keeps the whole ``k * D`` stack in ``obs``; ``gather`` rebuilds the
+stacked rows, bit for bit the rows full storage would hold (tests/rollout_frames_ref.py).
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import torch
@@ -31,6 +42,11 @@ from . import _lib
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+# The fields of SB3's RolloutBufferSamples (common/type_aliases.py), in its order.
+RolloutSamples = collections.namedtuple(
+    "RolloutSamples", ("observations", "actions", "old_values", "old_log_prob", "advantages", "returns"))
 
 
 class DeviceRollout:
@@ -51,13 +67,27 @@ class DeviceRollout:
     is treated as a termination); ``counts()`` reports how many.
 
     ``reward_dtype`` is the dtype ``put_step`` will be given (float32: an f32 env or
-    ``DeviceWrappers.norm_rew``; float64: an f64 env).  There is no CPU fallback."""
+    ``DeviceWrappers.norm_rew``; float64: an f64 env).  There is no CPU fallback.
+
+    ``n_stack=k`` (frame mode; ``obs_width`` must be ``k * D``): ``obs`` is None and ``frames``
+    [N, T + k - 1, D] holds one frame per (step, env): ``put_obs(0, ...)`` stores the whole window,
+    ``put_obs(t > 0, ...)`` its newest ``D`` columns, and ``gather`` rebuilds the stacks from ``frames``
+    and ``start``.  This needs the windows given to ``put_obs`` to evolve by the ``VecFrameStack`` rule
+    between ``put_obs(0)`` and the last ``put_obs`` of a rollout, with exactly the dones given to
+    ``put_step``: the fused loop of the module docstring does.  A manual ``wr.reset(obs, mask)`` inside a
+    rollout is not supported in frame mode (between rollouts it is).  ``clear_keeps_sign`` must be the
+    ``DeviceWrappers``' own setting: a slot behind an episode boundary is +0.0, or ``frame * 0.0``.
+    ``term_obs`` stays full width."""
 
     def __init__(self, num_envs, n_steps, obs_width, act_dim, device, reward_dtype=torch.float32, term_cap=None,
-                 lib_path=None):
+                 lib_path=None, n_stack=None, clear_keeps_sign=False):
         n, T, W, A = int(num_envs), int(n_steps), int(obs_width), int(act_dim)
         if n <= 0 or T <= 0 or W <= 0 or A <= 0:
             raise ValueError("num_envs, n_steps, obs_width and act_dim must be > 0")
+        if n_stack is not None:
+            n_stack = int(n_stack)
+            if not 1 <= n_stack <= 32 or W % n_stack != 0:
+                raise ValueError("n_stack must be in [1, 32] and divide obs_width")
         cap = 2 * n if term_cap is None else int(term_cap)
         if cap < 0:
             raise ValueError("term_cap must be >= 0")
@@ -70,7 +100,12 @@ class DeviceRollout:
         self.n, self.n_steps, self.w, self.a, self.term_cap = n, T, W, A, cap
         self.device, self.reward_dtype = device, reward_dtype
         f4 = dict(dtype=torch.float32, device=device)
-        self.obs = torch.zeros((T, n, W), **f4)
+        self.n_stack = n_stack
+        self.clear_keeps_sign = bool(clear_keeps_sign)
+        if n_stack is None:
+            self.obs, self.frames = torch.zeros((T, n, W), **f4), None
+        else:
+            self.obs, self.frames = None, torch.zeros((n, T + n_stack - 1, W // n_stack), **f4)
         self.act = torch.zeros((T, n, A), **f4)
         self.rew, self.val, self.logp, self.adv, self.ret = (torch.zeros((T, n), **f4) for _ in range(5))
         self.start = torch.zeros((T + 1, n), dtype=torch.uint8, device=device)
@@ -79,14 +114,21 @@ class DeviceRollout:
         self.term_obs = torch.zeros((max(cap, 1), W), **f4)[:cap]
         self._count = torch.zeros(2, dtype=torch.int32, device=device)
         self._scratch = torch.zeros(self.lib.usv_rollout_scratch_bytes(n) // 8, dtype=torch.int64, device=device)
+        self._bad = torch.zeros(1, dtype=torch.int32, device=device)
         self._bind()
 
     def _bind(self):
         """The C struct over the current buffers (again after a buffer was replaced)."""
+        # frame mode: put_step and gae refuse a NULL obs and never touch it, so it names the frames
+        k = self.n_stack
         self._ro = _lib.UsvRollout(self.n, self.n_steps, self.w, self.a, self.term_cap, 0, *(t.data_ptr() for t in (
-            self.obs, self.act, self.rew, self.val, self.logp, self.adv, self.ret, self.start, self.term_slot,
-            self.term_obs, self._count, self._scratch)))
+            self.obs if k is None else self.frames, self.act, self.rew, self.val, self.logp, self.adv, self.ret,
+            self.start, self.term_slot, self.term_obs, self._count, self._scratch)))
         self._rp = ctypes.byref(self._ro)
+        flags = _lib.ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN if self.clear_keeps_sign else 0
+        self._fr = _lib.UsvRolloutFrames(k or 1, self.w // (k or 1), flags, self.frames.data_ptr() if k else None,
+                                         self._bad.data_ptr())
+        self._fp = ctypes.byref(self._fr)
 
     def _check(self, name, t, dtype, shape):
         if t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous():
@@ -115,6 +157,10 @@ class DeviceRollout:
         self._check("val", val, torch.float32, (n,))
         self._check("logp", logp, torch.float32, (n,))
         stride = obs.stride(0) if n > 1 else W
+        if self.n_stack is not None:
+            _lib.check(self.lib.usv_rollout_put_obs_frames(self._rp, self._fp, t, _ptr(obs), stride, _ptr(act),
+                                                           _ptr(val), _ptr(logp), self._stream()), self.lib)
+            return
         _lib.check(self.lib.usv_rollout_put_obs(self._rp, t, _ptr(obs), stride, _ptr(act), _ptr(val), _ptr(logp),
                                                 self._stream()), self.lib)
 
@@ -156,3 +202,43 @@ class DeviceRollout:
         ints: one host copy, the only sync of this class."""
         c = self._count.tolist()
         return int(c[0]), int(c[1])
+
+    def gather(self, idx, out=None):
+        """SB3's ``RolloutBuffer._get_samples`` in one launch: the samples at the flat indices ``idx``
+        (int64 [B] on the device, ``t * N + e``: the ``[T, N] -> [T * N]`` reshape) as a
+        ``RolloutSamples`` of ``observations`` [B, W], ``actions`` [B, A] and ``old_values`` /
+        ``old_log_prob`` / ``advantages`` / ``returns`` [B].  In frame mode the observations are rebuilt
+        from ``frames`` and ``start``; they equal the rows full storage holds bit for bit.  The outputs
+        are fresh tensors, or those of ``out`` (a ``RolloutSamples`` of contiguous float32 tensors of
+        these shapes).  Runs on the current stream without a host sync.  An index outside [0, T * N) is
+        not dereferenced: its outputs are NaN and ``bad_indices()`` counts it."""
+        B = int(idx.shape[0]) if idx.dim() == 1 else 0
+        if idx.dtype != torch.int64 or not 0 < B < 2 ** 31 or idx.device != self.device:
+            raise ValueError(f"idx must be a non-empty 1-D int64 tensor (below 2^31 indices) on {self.device}")
+        idx = idx.contiguous()
+        shapes = ((B, self.w), (B, self.a), (B,), (B,), (B,), (B,))
+        if out is None:
+            out = RolloutSamples(*(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes))
+        else:
+            for name, t, s in zip(RolloutSamples._fields, out, shapes):
+                self._check(f"out.{name}", t, torch.float32, s)
+        _lib.check(self.lib.usv_rollout_gather(self._rp, self._fp, _ptr(idx), B, *(_ptr(t) for t in out),
+                                               self._stream()), self.lib)
+        return out if isinstance(out, RolloutSamples) else RolloutSamples(*out)
+
+    def get(self, batch_size, generator=None):
+        """SB3's ``RolloutBuffer.get``: one ``torch.randperm(T * N)`` on the device (``generator``: a
+        device generator), then ``gather`` of consecutive slices of ``batch_size`` indices; the last
+        slice may be shorter.  Call it after ``gae``."""
+        batch_size = int(batch_size)
+        if batch_size <= 0:
+            raise ValueError("batch_size must be > 0")
+        M = self.n_steps * self.n
+        perm = torch.randperm(M, device=self.device, generator=generator)
+        for s in range(0, M, batch_size):
+            yield self.gather(perm[s:s + batch_size])
+
+    def bad_indices(self):
+        """How many indices ``gather`` has refused since this object was built, as a Python int (one
+        host copy: a sync, like ``counts``)."""
+        return int(self._bad.item())

@@ -467,6 +467,47 @@ int usv_rollout_put_step(const usv_rollout* ro, int32_t t, const void* rew_dev, 
 int usv_rollout_gae(const usv_rollout* ro, const float* last_val_dev, const float* term_val_dev, double gamma,
                     double gae_lambda, void* stream);
 
+/* Frame-deduplicated obs storage and the minibatch gather: the other half of SB3's RolloutBuffer
+ * (get / _get_samples) and a rollout that keeps one D-float frame per (step, env) where usv_rollout.obs
+ * keeps the whole k-frame stack.  Additive (ABI v5 addition); usv_rollout is unchanged.
+ *
+ * frames is [n][T + k - 1][D] float32, env-major: row r of env e is the frame pushed at time r - (k - 1),
+ * so the k frames of sample (t, e) are the k D contiguous floats from row t on.
+ *
+ * usv_rollout_put_obs_frames(ro, fr, t, ...) replaces usv_rollout_put_obs (same source contract; act, val
+ * and logp are stored as there): at t = 0 the whole [k D] window goes to rows 0 .. k - 1 of each env, at
+ * t > 0 its newest D columns go to row t + k - 1.  Precondition: from put_obs(0) to the last put_obs of
+ * a rollout the windows evolve by the VecFrameStack rule with exactly the dones given to
+ * usv_rollout_put_step (a window reset by hand inside a rollout is not supported).  ro->obs is not read;
+ * usv_rollout_put_step and usv_rollout_gae still refuse a NULL obs and never touch it: point it at frames.
+ *
+ * usv_rollout_gather(ro, fr, idx_dev [B] int64, B, out...): for sample i = idx[b] = t * n + e, one launch
+ * writes obs_out[b] = the stacked row [W] that full storage would hold in obs[t][e], bit for bit, and
+ * act_out[b] [act_dim], val_out / logp_out / adv_out / ret_out [b] = act / val / logp / adv / ret at i.
+ *   Slot j of the row (0 = oldest) is the frame of time u = t - (k - 1 - j), cleared if some s with
+ *   max(u, 0) < s <= t has start[s][e] != 0; a cleared element is +0.0, or x * 0.0f (-0.0 where x was
+ *   negative) with USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN, as usv_wrap's USV_WRAP_CLEAR_KEEPS_SIGN.
+ *   fr->frames == NULL: full storage, the row is obs[i] (k * d must still equal obs_width; k = 1 will do).
+ *   An idx outside [0, T n) is not dereferenced: its outputs are NaN and *bad_count is incremented (it
+ *   is never reset by the library); the call still returns USV_OK.
+ *
+ * USV_ERR_ARG, before any HIP call, for a NULL struct, k < 1, d < 1, k > 32, k * d != obs_width, unknown
+ * flags, B <= 0, a NULL idx, output or bad_count, usv_rollout_put_obs_frames with frames == NULL, and
+ * everything usv_rollout_put_obs refuses. */
+#define USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN 1
+typedef struct usv_rollout_frames {
+  int32_t k, d;                /* n_stack and floats per frame; k * d == obs_width */
+  int32_t flags;               /* USV_ROLLOUT_FRAMES_* */
+  float* frames;               /* [n][T + k - 1][d], or NULL: full storage (gather only) */
+  int32_t* bad_count;          /* [1] indices the gather refused */
+} usv_rollout_frames;
+int usv_rollout_put_obs_frames(const usv_rollout* ro, const usv_rollout_frames* fr, int32_t t,
+                               const float* obs_src_dev, size_t obs_row_stride_floats, const float* act_dev,
+                               const float* val_dev, const float* logp_dev, void* stream);
+int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, const int64_t* idx_dev, int32_t B,
+                       float* obs_out, float* act_out, float* val_out, float* logp_out, float* adv_out,
+                       float* ret_out, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
