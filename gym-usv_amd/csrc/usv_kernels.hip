@@ -15,6 +15,7 @@
 //   usv_legacy.hpp        usv-asmc-v0 and the legacy float64 family
 //   usv_noscan_step.hpp   scan-free step (ignore_obstacles)
 //   usv_wrap_layout.hpp   the fused wrappers' frame ring: slots, stride, window (host C++, no HIP)
+//   usv_row_copy.hpp      the trainer kernels' row copy: 16-B pieces at 4-B alignment, optional transform
 //   usv_wrap.hpp          frame stack + episode statistics behind the step (usv_wrap_step / _reset)
 //   usv_norm_math.hpp     VecNormalize: moments arithmetic, work split, transform (host C++, no HIP)
 //   usv_norm.hpp          VecNormalize in front of the frame stack (usv_wrap_step_norm / _reset_norm)
@@ -843,8 +844,54 @@ size_t usv_wrap_window_offset(int32_t obs_dim, int32_t n_stack, int64_t j) {
   return obs_dim > 0 && n_stack >= 1 && j >= 0 ? wrap_window_offset(obs_dim, n_stack, j) : 0;
 }
 
-// The shape checks (before any HIP call), then the buffers' device; fills the kernel's arguments.
-static int wrap_args(const usv_wrap* w, int64_t j, std::initializer_list<const void*> more, WrapArgs& a, int& dev) {
+// One buffer of a trainer entry.  al: its alignment, a power of two; opt: it may be null.
+struct Buf {
+  const void* p;
+  uintptr_t al;
+  bool opt = false;
+};
+using Bufs = std::initializer_list<Buf>;
+enum BufFault { kBufOk = 0, kBufNull, kBufAlign, kBufDevice };
+constexpr size_t kMaxBufs = 32;        // of one call: its struct's and its own
+
+// The first fault among b[0 .. n): a null buffer that may not be null, then a misaligned one.  With dev,
+// then one that is no device pointer on the device of b[0]; *dev is that device, -1 if b[0] is on none.
+// Without dev there is no HIP call.
+static BufFault check_bufs(const Buf* b, size_t n, int* dev = nullptr) {
+  for (size_t i = 0; i < n; ++i)
+    if (!b[i].p && !b[i].opt) return kBufNull;
+  for (size_t i = 0; i < n; ++i)
+    if ((reinterpret_cast<uintptr_t>(b[i].p) & (b[i].al - 1)) != 0) return kBufAlign;
+  if (!dev) return kBufOk;
+  *dev = -1;
+  for (size_t i = 0; i < n; ++i) {
+    if (!b[i].p) continue;
+    hipPointerAttribute_t pa{};
+    const int d = hipPointerGetAttributes(&pa, b[i].p) == hipSuccess ? pa.device : -1;
+    if (i == 0) *dev = d;
+    if (d < 0 || d != *dev) {
+      (void)hipGetLastError();
+      return kBufDevice;
+    }
+  }
+  return kBufOk;
+}
+static BufFault check_bufs(Bufs b) { return check_bufs(b.begin(), b.size()); }
+
+// The launch geometry of the kernels whose waves own kWrapEnvs envs each.
+static dim3 wrap_grid(int n) { return dim3((n + kWaves * kWrapEnvs - 1) / (kWaves * kWrapEnvs)); }
+
+static size_t norm_bufs(const usv_norm* z, Buf* out) {
+  const void* const ptrs[] = {z->obs_mean, z->obs_var, z->obs_inv_std, z->obs_count, z->ret_mean, z->ret_var,
+                              z->ret_inv_std, z->ret_count, z->returns, z->scratch};
+  size_t n = 0;
+  for (const void* p : ptrs) out[n++] = Buf{p, 8};
+  return n;
+}
+
+// The shape checks (before any HIP call), then the buffers' device (`more`: the call's own; zn's, if
+// given, have passed norm_check); fills the kernel's arguments.
+static int wrap_args(const usv_wrap* w, const usv_norm* zn, int64_t j, Bufs more, WrapArgs& a, int& dev) {
   if (!w) return fail(USV_ERR_ARG, "null usv_wrap");
   if (w->n <= 0 || w->obs_dim <= 0 || w->n_stack < 1)
     return fail(USV_ERR_ARG, "usv_wrap: n and obs_dim must be > 0 and n_stack >= 1");
@@ -856,26 +903,18 @@ static int wrap_args(const usv_wrap* w, int64_t j, std::initializer_list<const v
   if (!w->ep_ret || !w->ep_len) return fail(USV_ERR_ARG, "usv_wrap: null ep_ret / ep_len");
   if (!!w->cum_ret != !!w->cum_len || !!w->cum_ret != !!w->cum_eps)
     return fail(USV_ERR_ARG, "usv_wrap: cum_ret, cum_len and cum_eps are given together or not at all");
-  for (const void* p : more)
-    if (!p) return fail(USV_ERR_ARG, "usv_wrap: null argument");
-  auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
-  if (misaligned(w->ring, 4) || misaligned(w->ep_len, 4) || misaligned(w->ep_ret, 8) || misaligned(w->episode, 8) ||
-      misaligned(w->cum_ret, 8) || misaligned(w->cum_len, 8) || misaligned(w->cum_eps, 8))
-    return fail(USV_ERR_ARG, "usv_wrap: a buffer is not aligned to its element size");
-  auto device_of = [](const void* p) {
-    hipPointerAttribute_t pa{};
-    return hipPointerGetAttributes(&pa, p) == hipSuccess ? pa.device : -1;
-  };
-  dev = device_of(w->ring);
-  if (dev < 0) { (void)hipGetLastError(); return fail(USV_ERR_ARG, "usv_wrap: ring is not a device pointer"); }
-  bool same = true;
-  for (const void* p : {(const void*)w->ep_ret, (const void*)w->ep_len, (const void*)w->episode,
-                        (const void*)w->cum_ret, (const void*)w->cum_len, (const void*)w->cum_eps})
-    same = same && (!p || device_of(p) == dev);
-  for (const void* p : more) same = same && device_of(p) == dev;
-  if (!same) {
-    (void)hipGetLastError();
-    return fail(USV_ERR_ARG, "usv_wrap: a buffer is not a device pointer on the ring's device");
+  Buf all[kMaxBufs] = {{w->ring, 4},          {w->ep_ret, 8},        {w->ep_len, 4},       {w->episode, 8, true},
+                       {w->cum_ret, 8, true}, {w->cum_len, 8, true}, {w->cum_eps, 8, true}};
+  size_t nb = 7;
+  for (const Buf& b : more) all[nb++] = b;
+  if (zn) nb += norm_bufs(zn, all + nb);
+  switch (check_bufs(all, nb, &dev)) {
+    case kBufNull: return fail(USV_ERR_ARG, "usv_wrap: null argument");
+    case kBufAlign: return fail(USV_ERR_ARG, "usv_wrap: a buffer is not aligned to its element size");
+    case kBufDevice:
+      return fail(USV_ERR_ARG, dev < 0 ? "usv_wrap: ring is not a device pointer"
+                                       : "usv_wrap: a buffer is not a device pointer on the ring's device");
+    case kBufOk: break;
   }
   const int k = w->n_stack;
   a = WrapArgs{w->n, w->obs_dim, k, w->reward_bytes, wrap_slot(j, k), wrap_mirror_slot(j, k),
@@ -884,61 +923,12 @@ static int wrap_args(const usv_wrap* w, int64_t j, std::initializer_list<const v
   return USV_OK;
 }
 
-int usv_wrap_reset(const usv_wrap* w, int64_t j, const uint8_t* mask, const float* obs, void* stream) {
-  WrapArgs a;
-  int dev;
-  if (int rc = wrap_args(w, j, {obs}, a, dev)) return rc;
-  if (mask) {
-    hipPointerAttribute_t pa{};
-    if (hipPointerGetAttributes(&pa, mask) != hipSuccess || pa.device != dev) {
-      (void)hipGetLastError();
-      return fail(USV_ERR_ARG, "usv_wrap: mask is not a device pointer on the ring's device");
-    }
-  }
-  if ((reinterpret_cast<uintptr_t>(obs) & 3) != 0) return fail(USV_ERR_ARG, "usv_wrap: obs is not 4-B aligned");
-  DeviceGuard g(dev);
-  const int per_block = kWaves * kWrapEnvs;
-  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
-  if (mask)
-    hipLaunchKernelGGL(wrap_reset_kernel<true>, grid, block, 0, (hipStream_t)stream, a, mask, obs);
-  else
-    hipLaunchKernelGGL(wrap_reset_kernel<false>, grid, block, 0, (hipStream_t)stream, a, mask, obs);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
-}
-
-int usv_wrap_step(const usv_wrap* w, int64_t j, const float* obs, const void* rew, const uint8_t* done,
-                  const float* final_obs, float* final_stack, void* stream) {
-  WrapArgs a;
-  int dev;
-  if (final_stack && !final_obs && w && w->n > 0 && w->obs_dim > 0 && w->n_stack >= 1 && w->ring)
-    return fail(USV_ERR_ARG, "usv_wrap_step: final_stack needs final_obs");
-  int rc = final_stack ? wrap_args(w, j, {obs, rew, done, final_obs, final_stack}, a, dev)
-                       : wrap_args(w, j, {obs, rew, done}, a, dev);
-  if (rc) return rc;
-  auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
-  if (misaligned(obs, 4) || misaligned(rew, a.reward_bytes) || (final_stack && (misaligned(final_obs, 4) || misaligned(final_stack, 4))))
-    return fail(USV_ERR_ARG, "usv_wrap_step: a buffer is not aligned to its element size");
-  DeviceGuard g(dev);
-  const int per_block = kWaves * kWrapEnvs;
-  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
-  const float* const fobs = final_stack ? final_obs : nullptr;
-  if (a.reward_bytes == 8)
-    hipLaunchKernelGGL(wrap_step_kernel<double>, grid, block, 0, (hipStream_t)stream, a, obs, (const double*)rew,
-                       done, fobs, final_stack);
-  else
-    hipLaunchKernelGGL(wrap_step_kernel<float>, grid, block, 0, (hipStream_t)stream, a, obs, (const float*)rew,
-                       done, fobs, final_stack);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
-}
-
 // ---- fused VecNormalize (usv_norm.hpp) in front of the frame stack
 size_t usv_norm_scratch_bytes(int32_t n, int32_t obs_dim) {
   return n > 0 && obs_dim > 0 ? (size_t)2 * norm_num_partials(n) * ((size_t)obs_dim + 1) * sizeof(double) : 0;
 }
 
-// The checks that need no HIP call; the device of every pointer is wrap_args's to check (norm_ptrs).
+// The checks that need no HIP call; the device of every pointer is wrap_args's to check.
 static int norm_check(const usv_wrap* w, const usv_norm* z) {
   if (!z) return fail(USV_ERR_ARG, "null usv_norm");
   if (z->n <= 0 || z->obs_dim <= 0) return fail(USV_ERR_ARG, "usv_norm: n and obs_dim must be > 0");
@@ -950,13 +940,12 @@ static int norm_check(const usv_wrap* w, const usv_norm* z) {
   if (!(z->clip_obs >= 0.0) || !(z->clip_reward >= 0.0)) return fail(USV_ERR_ARG, "usv_norm: clip_obs and clip_reward must be >= 0");
   if (!(z->gamma >= 0.0 && z->gamma <= 1.0)) return fail(USV_ERR_ARG, "usv_norm: gamma must be in [0, 1]");
   if (!(z->epsilon > 0.0)) return fail(USV_ERR_ARG, "usv_norm: epsilon must be > 0");
-  const void* const ptrs[] = {z->obs_mean, z->obs_var, z->obs_inv_std, z->obs_count, z->ret_mean, z->ret_var,
-                              z->ret_inv_std, z->ret_count, z->returns, z->scratch};
-  for (const void* p : ptrs) {
-    if (!p) return fail(USV_ERR_ARG, "usv_norm: null buffer");
-    if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return fail(USV_ERR_ARG, "usv_norm: a buffer is not 8-B aligned");
+  Buf own[kMaxBufs];
+  switch (check_bufs(own, norm_bufs(z, own))) {
+    case kBufNull: return fail(USV_ERR_ARG, "usv_norm: null buffer");
+    case kBufAlign: return fail(USV_ERR_ARG, "usv_norm: a buffer is not 8-B aligned");
+    default: return USV_OK;
   }
-  return USV_OK;
 }
 
 static NormArgs norm_args(const usv_norm* z, bool update) {
@@ -967,8 +956,8 @@ static NormArgs norm_args(const usv_norm* z, bool update) {
                   z->ret_count, z->returns, z->scratch};
 }
 
-// Launches 1 and 2 of usv_norm.hpp (nothing if the call updates no statistic).
 extern "C++" {
+// Launches 1 and 2 of usv_norm.hpp (nothing if the call updates no statistic).
 template <typename RW>
 static void norm_reduce(const NormArgs& z, const float* obs, const RW* rew, hipStream_t s) {
   if (!z.upd_obs && !z.upd_ret) return;
@@ -976,83 +965,98 @@ static void norm_reduce(const NormArgs& z, const float* obs, const RW* rew, hipS
   hipLaunchKernelGGL(norm_moments_kernel<RW>, dim3(P), dim3(kBlock), 0, s, z, obs, rew);
   hipLaunchKernelGGL(norm_finalise_kernel, dim3(z.D + 1), dim3(kNormLanes), 0, s, z, P);
 }
+
+// The reset's launches; zn null: no normalisation.
+template <bool MASKED>
+static void wrap_reset_launch(const WrapArgs& a, const usv_norm* zn, const uint8_t* mask, const float* obs, hipStream_t s) {
+  const dim3 grid = wrap_grid(a.n), block(kBlock);
+  if (!zn) {
+    hipLaunchKernelGGL(wrap_reset_kernel<MASKED>, grid, block, 0, s, a, mask, obs);
+    return;
+  }
+  NormArgs z = norm_args(zn, !MASKED);                  // a masked reset updates no statistic
+  z.upd_ret = 0;
+  norm_reduce<float>(z, obs, nullptr, s);
+  if ((zn->flags & USV_NORM_OBS) != 0)
+    hipLaunchKernelGGL((wrap_reset_norm_kernel<MASKED, true>), grid, block, (size_t)16 * a.D, s, a, z, mask, obs);
+  else
+    hipLaunchKernelGGL((wrap_reset_norm_kernel<MASKED, false>), grid, block, 0, s, a, z, mask, obs);
+}
+
+// The step's launches; zn null: no normalisation.
+template <typename RW>
+static void wrap_step_launch(const WrapArgs& a, const usv_norm* zn, const float* obs, const RW* rew, const uint8_t* done,
+                             const float* fobs, float* final_stack, float* norm_rew_out, hipStream_t s) {
+  const dim3 grid = wrap_grid(a.n), block(kBlock);
+  if (!zn) {
+    hipLaunchKernelGGL(wrap_step_kernel<RW>, grid, block, 0, s, a, obs, rew, done, fobs, final_stack);
+    return;
+  }
+  const NormArgs z = norm_args(zn, true);
+  norm_reduce<RW>(z, obs, rew, s);
+  if ((zn->flags & USV_NORM_OBS) != 0)
+    hipLaunchKernelGGL((wrap_step_norm_kernel<RW, true>), grid, block, (size_t)16 * a.D, s, a, z, obs, rew, done, fobs,
+                       final_stack, norm_rew_out);
+  else
+    hipLaunchKernelGGL((wrap_step_norm_kernel<RW, false>), grid, block, 0, s, a, z, obs, rew, done, fobs, final_stack,
+                       norm_rew_out);
+}
+}
+
+// usv_wrap_reset and, with a usv_norm that has passed norm_check, usv_wrap_reset_norm.
+static int wrap_reset(const usv_wrap* w, const usv_norm* zn, int64_t j, const uint8_t* mask, const float* obs,
+                      void* stream) {
+  WrapArgs a;
+  int dev;
+  if (int rc = wrap_args(w, zn, j, {{obs, 4}, {mask, 1, true}}, a, dev)) return rc;
+  DeviceGuard g(dev);
+  if (mask) wrap_reset_launch<true>(a, zn, mask, obs, (hipStream_t)stream);
+  else wrap_reset_launch<false>(a, zn, mask, obs, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// usv_wrap_step and, with a usv_norm that has passed norm_check, usv_wrap_step_norm.
+static int wrap_step(const usv_wrap* w, const usv_norm* zn, int64_t j, const float* obs, const void* rew,
+                     const uint8_t* done, const float* final_obs, float* final_stack, float* norm_rew_out, void* stream) {
+  WrapArgs a;
+  int dev;
+  if (final_stack && !final_obs && w && w->n > 0 && w->obs_dim > 0 && w->n_stack >= 1 && w->ring)
+    return fail(USV_ERR_ARG, "usv_wrap_step: final_stack needs final_obs");
+  const float* const fobs = final_stack ? final_obs : nullptr;   // read only with final_stack
+  const uintptr_t rb = w ? (uintptr_t)w->reward_bytes : 4;       // wrap_args refuses any but 4 and 8
+  if (int rc = wrap_args(w, zn, j, {{obs, 4}, {rew, rb}, {done, 1}, {fobs, 4, true}, {final_stack, 4, true},
+                                    {norm_rew_out, 4, !zn}}, a, dev))
+    return rc;
+  DeviceGuard g(dev);
+  if (a.reward_bytes == 8)
+    wrap_step_launch(a, zn, obs, (const double*)rew, done, fobs, final_stack, norm_rew_out, (hipStream_t)stream);
+  else
+    wrap_step_launch(a, zn, obs, (const float*)rew, done, fobs, final_stack, norm_rew_out, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_wrap_reset(const usv_wrap* w, int64_t j, const uint8_t* mask, const float* obs, void* stream) {
+  return wrap_reset(w, nullptr, j, mask, obs, stream);
+}
+
+int usv_wrap_step(const usv_wrap* w, int64_t j, const float* obs, const void* rew, const uint8_t* done,
+                  const float* final_obs, float* final_stack, void* stream) {
+  return wrap_step(w, nullptr, j, obs, rew, done, final_obs, final_stack, nullptr, stream);
 }
 
 int usv_wrap_reset_norm(const usv_wrap* w, const usv_norm* zn, int64_t j, const uint8_t* mask, const float* obs,
                         void* stream) {
-  WrapArgs a;
-  int dev;
   if (int rc = norm_check(w, zn)) return rc;
-  if (int rc = wrap_args(w, j, {obs, zn->obs_mean, zn->obs_var, zn->obs_inv_std, zn->obs_count, zn->ret_mean,
-                                zn->ret_var, zn->ret_inv_std, zn->ret_count, zn->returns, zn->scratch}, a, dev))
-    return rc;
-  if (mask) {
-    hipPointerAttribute_t pa{};
-    if (hipPointerGetAttributes(&pa, mask) != hipSuccess || pa.device != dev) {
-      (void)hipGetLastError();
-      return fail(USV_ERR_ARG, "usv_wrap: mask is not a device pointer on the ring's device");
-    }
-  }
-  if ((reinterpret_cast<uintptr_t>(obs) & 3) != 0) return fail(USV_ERR_ARG, "usv_wrap: obs is not 4-B aligned");
-  DeviceGuard g(dev);
-  NormArgs z = norm_args(zn, mask == nullptr);          // a masked reset updates no statistic
-  z.upd_ret = 0;
-  const hipStream_t s = (hipStream_t)stream;
-  norm_reduce<float>(z, obs, nullptr, s);
-  const int per_block = kWaves * kWrapEnvs;
-  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
-  const bool no = (zn->flags & USV_NORM_OBS) != 0;
-  const size_t lds = no ? (size_t)16 * a.D : 0;
-  if (mask) {
-    if (no) hipLaunchKernelGGL((wrap_reset_norm_kernel<true, true>), grid, block, lds, s, a, z, mask, obs);
-    else hipLaunchKernelGGL((wrap_reset_norm_kernel<true, false>), grid, block, lds, s, a, z, mask, obs);
-  } else {
-    if (no) hipLaunchKernelGGL((wrap_reset_norm_kernel<false, true>), grid, block, lds, s, a, z, mask, obs);
-    else hipLaunchKernelGGL((wrap_reset_norm_kernel<false, false>), grid, block, lds, s, a, z, mask, obs);
-  }
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return wrap_reset(w, zn, j, mask, obs, stream);
 }
 
 int usv_wrap_step_norm(const usv_wrap* w, const usv_norm* zn, int64_t j, const float* obs, const void* rew,
                        const uint8_t* done, const float* final_obs, float* final_stack, float* norm_rew_out,
                        void* stream) {
-  WrapArgs a;
-  int dev;
   if (int rc = norm_check(w, zn)) return rc;
-  if (final_stack && !final_obs && w && w->n > 0 && w->obs_dim > 0 && w->n_stack >= 1 && w->ring)
-    return fail(USV_ERR_ARG, "usv_wrap_step: final_stack needs final_obs");
-  const void* const fo = final_stack ? (const void*)final_obs : (const void*)obs;   // checked only with final_stack
-  const void* const fs = final_stack ? (const void*)final_stack : (const void*)obs;
-  if (int rc = wrap_args(w, j, {obs, rew, done, fo, fs, norm_rew_out, zn->obs_mean, zn->obs_var, zn->obs_inv_std,
-                                zn->obs_count, zn->ret_mean, zn->ret_var, zn->ret_inv_std, zn->ret_count, zn->returns,
-                                zn->scratch}, a, dev))
-    return rc;
-  auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
-  if (misaligned(obs, 4) || misaligned(rew, a.reward_bytes) || misaligned(norm_rew_out, 4) ||
-      (final_stack && (misaligned(final_obs, 4) || misaligned(final_stack, 4))))
-    return fail(USV_ERR_ARG, "usv_wrap_step: a buffer is not aligned to its element size");
-  DeviceGuard g(dev);
-  const NormArgs z = norm_args(zn, true);
-  const hipStream_t s = (hipStream_t)stream;
-  const int per_block = kWaves * kWrapEnvs;
-  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
-  const float* const fobs = final_stack ? final_obs : nullptr;
-  const bool no = (zn->flags & USV_NORM_OBS) != 0;
-  const size_t lds = no ? (size_t)16 * a.D : 0;
-  if (a.reward_bytes == 8) {
-    const double* const r = (const double*)rew;
-    norm_reduce<double>(z, obs, r, s);
-    if (no) hipLaunchKernelGGL((wrap_step_norm_kernel<double, true>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
-    else hipLaunchKernelGGL((wrap_step_norm_kernel<double, false>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
-  } else {
-    const float* const r = (const float*)rew;
-    norm_reduce<float>(z, obs, r, s);
-    if (no) hipLaunchKernelGGL((wrap_step_norm_kernel<float, true>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
-    else hipLaunchKernelGGL((wrap_step_norm_kernel<float, false>), grid, block, lds, s, a, z, obs, r, done, fobs, final_stack, norm_rew_out);
-  }
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return wrap_step(w, zn, j, obs, rew, done, final_obs, final_stack, norm_rew_out, stream);
 }
 
 // ---- device rollout buffer (usv_rollout.hpp)
@@ -1060,37 +1064,28 @@ size_t usv_rollout_scratch_bytes(int32_t n) {
   return n > 0 ? 2 * sizeof(long long) + (((size_t)ro_num_chunks(n) * sizeof(int32_t) + 7) & ~(size_t)7) : 0;
 }
 
-// The checks that need no HIP call (`more`: the call's own buffers, all 4-B aligned or coarser), then the
-// device of every buffer; fills the kernels' arguments.
-static int rollout_args(const usv_rollout* ro, bool in_range, std::initializer_list<const void*> more, RoArgs& a,
-                        int& dev) {
+// The checks that need no HIP call, then the device of every buffer (`more`: the call's own); fills the
+// kernels' arguments.
+static int rollout_args(const usv_rollout* ro, bool in_range, Bufs more, RoArgs& a, int& dev) {
   if (!ro) return fail(USV_ERR_ARG, "null usv_rollout");
   if (ro->n <= 0 || ro->n_steps <= 0 || ro->obs_width <= 0 || ro->act_dim <= 0)
     return fail(USV_ERR_ARG, "usv_rollout: n, n_steps, obs_width and act_dim must be > 0");
   if (ro->term_cap < 0 || ro->reserved != 0) return fail(USV_ERR_ARG, "usv_rollout: term_cap must be >= 0 and reserved 0");
   if (!in_range) return fail(USV_ERR_ARG, "usv_rollout: t must be in [0, n_steps)");
-  const void* const own[] = {ro->obs, ro->act, ro->rew, ro->val, ro->logp, ro->adv, ro->ret, ro->start,
-                             ro->term_slot, ro->term_count, ro->scratch, ro->term_cap > 0 ? ro->term_obs : ro->obs};
-  for (const void* p : own)
-    if (!p) return fail(USV_ERR_ARG, "usv_rollout: null buffer");
-  for (const void* p : more)
-    if (!p) return fail(USV_ERR_ARG, "usv_rollout: null argument");
-  auto misaligned = [](const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; };
-  for (const void* p : own)
-    if (p != (const void*)ro->start && misaligned(p, p == ro->scratch ? 8 : 4))
-      return fail(USV_ERR_ARG, "usv_rollout: a buffer is not aligned to its element size");
-  auto device_of = [](const void* p) {
-    hipPointerAttribute_t pa{};
-    return hipPointerGetAttributes(&pa, p) == hipSuccess ? pa.device : -1;
-  };
-  dev = device_of(ro->obs);
-  if (dev < 0) { (void)hipGetLastError(); return fail(USV_ERR_ARG, "usv_rollout: obs is not a device pointer"); }
-  bool same = true;
-  for (const void* p : own) same = same && device_of(p) == dev;
-  for (const void* p : more) same = same && device_of(p) == dev;
-  if (!same) {
-    (void)hipGetLastError();
-    return fail(USV_ERR_ARG, "usv_rollout: a buffer is not a device pointer on the device that holds obs");
+  Buf all[kMaxBufs] = {{ro->obs, 4},   {ro->act, 4},       {ro->rew, 4},        {ro->val, 4},
+                       {ro->logp, 4},  {ro->adv, 4},       {ro->ret, 4},        {ro->start, 1},
+                       {ro->term_slot, 4}, {ro->term_count, 4}, {ro->scratch, 8},
+                       {ro->term_cap > 0 ? (const void*)ro->term_obs : ro->obs, 4}};
+  size_t nb = 12;
+  if (check_bufs(all, nb) == kBufNull) return fail(USV_ERR_ARG, "usv_rollout: null buffer");
+  for (const Buf& b : more) all[nb++] = b;
+  switch (check_bufs(all, nb, &dev)) {
+    case kBufNull: return fail(USV_ERR_ARG, "usv_rollout: null argument");
+    case kBufAlign: return fail(USV_ERR_ARG, "usv_rollout: a buffer is not aligned to its element size");
+    case kBufDevice:
+      return fail(USV_ERR_ARG, dev < 0 ? "usv_rollout: obs is not a device pointer"
+                                       : "usv_rollout: a buffer is not a device pointer on the device that holds obs");
+    case kBufOk: break;
   }
   long long* const totals = (long long*)ro->scratch;
   a = RoArgs{ro->n, ro->n_steps, ro->obs_width, ro->act_dim, ro->term_cap, ro->obs, ro->act, ro->rew, ro->val,
@@ -1099,31 +1094,39 @@ static int rollout_args(const usv_rollout* ro, bool in_range, std::initializer_l
   return USV_OK;
 }
 
-// USV_ROLLOUT_STORE=wt | plain overrides the obs store's policy (tools/rollout_ab.py measures both).
-static bool rollout_store_wt() {
-  const char* const s = std::getenv("USV_ROLLOUT_STORE");
-  return s ? std::strcmp(s, "wt") == 0 : kRolloutStoreWt;
+// usv_rollout_put_obs and, with a usv_rollout_frames that has passed rollout_frames_check and has
+// frames, usv_rollout_put_obs_frames.
+static int rollout_put_obs(const usv_rollout* ro, const usv_rollout_frames* fr, int32_t t, const float* obs_src,
+                           size_t stride, const float* act, const float* val, const float* logp, void* stream) {
+  RoArgs a;
+  int dev;
+  const Bufs more = {{obs_src, 4}, {act, 4}, {val, 4}, {logp, 4}};
+  if (ro && ro->obs_width > 0 && stride < (size_t)ro->obs_width)
+    return fail(USV_ERR_ARG, "usv_rollout_put_obs: the row stride is below obs_width");
+  if (check_bufs(more) == kBufAlign) return fail(USV_ERR_ARG, "usv_rollout_put_obs: a buffer is not 4-B aligned");
+  usv_rollout r;
+  if (ro && fr) {
+    r = *ro;
+    r.obs = fr->frames;                                 // frame mode has no obs; the frames name the device
+    ro = &r;
+  }
+  if (int rc = rollout_args(ro, ro && t >= 0 && t < ro->n_steps, more, a, dev)) return rc;
+  DeviceGuard g(dev);
+  const dim3 grid = wrap_grid(a.n), block(kBlock);
+  if (fr) {
+    const RfArgs f{fr->k, fr->d, fr->flags & USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN, fr->frames, fr->bad_count};
+    hipLaunchKernelGGL(rollout_frames_obs_kernel, grid, block, 0, (hipStream_t)stream, a, f, (int)t, obs_src, stride, act,
+                       val, logp);
+  } else {
+    hipLaunchKernelGGL(rollout_obs_kernel, grid, block, 0, (hipStream_t)stream, a, (int)t, obs_src, stride, act, val, logp);
+  }
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
 }
 
 int usv_rollout_put_obs(const usv_rollout* ro, int32_t t, const float* obs_src, size_t stride, const float* act,
                         const float* val, const float* logp, void* stream) {
-  RoArgs a;
-  int dev;
-  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
-  if (ro && ro->obs_width > 0 && stride < (size_t)ro->obs_width)
-    return fail(USV_ERR_ARG, "usv_rollout_put_obs: the row stride is below obs_width");
-  if (misaligned(obs_src) || misaligned(act) || misaligned(val) || misaligned(logp))
-    return fail(USV_ERR_ARG, "usv_rollout_put_obs: a buffer is not 4-B aligned");
-  if (int rc = rollout_args(ro, ro && t >= 0 && t < ro->n_steps, {obs_src, act, val, logp}, a, dev)) return rc;
-  DeviceGuard g(dev);
-  const int per_block = kWaves * kWrapEnvs;
-  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
-  if (rollout_store_wt())
-    hipLaunchKernelGGL(rollout_obs_kernel<true>, grid, block, 0, (hipStream_t)stream, a, (int)t, obs_src, stride, act, val, logp);
-  else
-    hipLaunchKernelGGL(rollout_obs_kernel<false>, grid, block, 0, (hipStream_t)stream, a, (int)t, obs_src, stride, act, val, logp);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return rollout_put_obs(ro, nullptr, t, obs_src, stride, act, val, logp, stream);
 }
 
 int usv_rollout_put_step(const usv_rollout* ro, int32_t t, const void* rew, int32_t reward_bytes, const uint8_t* term,
@@ -1131,11 +1134,11 @@ int usv_rollout_put_step(const usv_rollout* ro, int32_t t, const void* rew, int3
   RoArgs a;
   int dev;
   if (reward_bytes != 4 && reward_bytes != 8) return fail(USV_ERR_ARG, "usv_rollout_put_step: reward_bytes must be 4 or 8");
-  if ((reinterpret_cast<uintptr_t>(rew) & (uintptr_t)(reward_bytes - 1)) != 0 || (reinterpret_cast<uintptr_t>(final_stack) & 3) != 0)
+  if (check_bufs({{rew, (uintptr_t)reward_bytes, true}, {final_stack, 4, true}}) == kBufAlign)
     return fail(USV_ERR_ARG, "usv_rollout_put_step: a buffer is not aligned to its element size");
   const bool need_fs = ro && ro->term_cap > 0;          // without slots no terminal row is ever read
   if (int rc = rollout_args(ro, ro && t >= 0 && t < ro->n_steps,
-                            {rew, term, trunc, need_fs ? (const void*)final_stack : rew}, a, dev))
+                            {{rew, 4}, {term, 1}, {trunc, 1}, {need_fs ? (const void*)final_stack : rew, 4}}, a, dev))
     return rc;
   DeviceGuard g(dev);
   const hipStream_t s = (hipStream_t)stream;
@@ -1155,10 +1158,10 @@ int usv_rollout_gae(const usv_rollout* ro, const float* last_val, const float* t
   int dev;
   if (!(gamma >= 0.0 && gamma <= 1.0) || !(gae_lambda >= 0.0 && gae_lambda <= 1.0))
     return fail(USV_ERR_ARG, "usv_rollout_gae: gamma and gae_lambda must be in [0, 1]");
-  if ((reinterpret_cast<uintptr_t>(last_val) & 3) != 0 || (reinterpret_cast<uintptr_t>(term_val) & 3) != 0)
+  if (check_bufs({{last_val, 4, true}, {term_val, 4, true}}) == kBufAlign)
     return fail(USV_ERR_ARG, "usv_rollout_gae: a buffer is not 4-B aligned");
   if (ro && ro->term_cap > 0 && !term_val) return fail(USV_ERR_ARG, "usv_rollout_gae: term_val is missing while term_cap > 0");
-  if (int rc = rollout_args(ro, true, {last_val, term_val ? (const void*)term_val : last_val}, a, dev)) return rc;
+  if (int rc = rollout_args(ro, true, {{last_val, 4}, {term_val ? term_val : last_val, 4}}, a, dev)) return rc;
   DeviceGuard g(dev);
   const dim3 grid((a.n + kBlock - 1) / kBlock), block(kBlock);
   hipLaunchKernelGGL(rollout_gae_kernel, grid, block, 0, (hipStream_t)stream, a, last_val, term_val, ro_g32(gamma),
@@ -1177,33 +1180,16 @@ static int rollout_frames_check(const usv_rollout* ro, const usv_rollout_frames*
   if ((int64_t)fr->k * fr->d != (int64_t)ro->obs_width)
     return fail(USV_ERR_ARG, "usv_rollout_frames: k * d must equal obs_width");
   if ((fr->flags & ~USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN) != 0) return fail(USV_ERR_ARG, "usv_rollout_frames: unknown flags");
-  if (((reinterpret_cast<uintptr_t>(fr->frames) | reinterpret_cast<uintptr_t>(fr->bad_count)) & 3) != 0)
+  if (check_bufs({{fr->frames, 4, true}, {fr->bad_count, 4, true}}) == kBufAlign)
     return fail(USV_ERR_ARG, "usv_rollout_frames: a buffer is not 4-B aligned");
   return USV_OK;
 }
 
 int usv_rollout_put_obs_frames(const usv_rollout* ro, const usv_rollout_frames* fr, int32_t t, const float* obs_src,
                                size_t stride, const float* act, const float* val, const float* logp, void* stream) {
-  RoArgs a;
-  int dev;
   if (int rc = rollout_frames_check(ro, fr)) return rc;
   if (!fr->frames) return fail(USV_ERR_ARG, "usv_rollout_put_obs_frames: the rollout has no frames");
-  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
-  if (ro->obs_width > 0 && stride < (size_t)ro->obs_width)
-    return fail(USV_ERR_ARG, "usv_rollout_put_obs_frames: the row stride is below obs_width");
-  if (misaligned(obs_src) || misaligned(act) || misaligned(val) || misaligned(logp))
-    return fail(USV_ERR_ARG, "usv_rollout_put_obs_frames: a buffer is not 4-B aligned");
-  usv_rollout r = *ro;
-  r.obs = fr->frames;                                   // frame mode has no obs; the frames name the device
-  if (int rc = rollout_args(&r, t >= 0 && t < ro->n_steps, {obs_src, act, val, logp}, a, dev)) return rc;
-  DeviceGuard g(dev);
-  const RfArgs f{fr->k, fr->d, fr->flags & USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN, fr->frames, fr->bad_count};
-  const int per_block = kWaves * kWrapEnvs;
-  const dim3 grid((a.n + per_block - 1) / per_block), block(kBlock);
-  hipLaunchKernelGGL(rollout_frames_obs_kernel, grid, block, 0, (hipStream_t)stream, a, f, (int)t, obs_src, stride, act,
-                     val, logp);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return rollout_put_obs(ro, fr, t, obs_src, stride, act, val, logp, stream);
 }
 
 int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, const int64_t* idx, int32_t B,
@@ -1215,15 +1201,15 @@ int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, cons
   if (B <= 0) return fail(USV_ERR_ARG, "usv_rollout_gather: B must be > 0");
   if (!fr->bad_count) return fail(USV_ERR_ARG, "usv_rollout_gather: null bad_count");
   if (!idx) return fail(USV_ERR_ARG, "usv_rollout_gather: null idx");
-  if (!obs_out || !act_out || !val_out || !logp_out || !adv_out || !ret_out)
-    return fail(USV_ERR_ARG, "usv_rollout_gather: null output");
+  const Bufs more = {{idx, 8},     {fr->bad_count, 4}, {obs_out, 4}, {act_out, 4},
+                     {val_out, 4}, {logp_out, 4},      {adv_out, 4}, {ret_out, 4}};
+  const BufFault of = check_bufs(more.begin() + 2, 6);  // the outputs
+  if (of == kBufNull) return fail(USV_ERR_ARG, "usv_rollout_gather: null output");
   if ((reinterpret_cast<uintptr_t>(idx) & 7) != 0) return fail(USV_ERR_ARG, "usv_rollout_gather: idx is not 8-B aligned");
-  for (const void* p : {obs_out, act_out, val_out, logp_out, adv_out, ret_out})
-    if ((reinterpret_cast<uintptr_t>(p) & 3) != 0) return fail(USV_ERR_ARG, "usv_rollout_gather: an output is not 4-B aligned");
+  if (of == kBufAlign) return fail(USV_ERR_ARG, "usv_rollout_gather: an output is not 4-B aligned");
   usv_rollout r = *ro;
   if (fr->frames) r.obs = fr->frames;
-  if (int rc = rollout_args(&r, true, {idx, fr->bad_count, obs_out, act_out, val_out, logp_out, adv_out, ret_out}, a, dev))
-    return rc;
+  if (int rc = rollout_args(&r, true, more, a, dev)) return rc;
   DeviceGuard g(dev);
   const RfArgs f{fr->k, fr->d, fr->flags & USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN, fr->frames, fr->bad_count};
   const int per_block = kWaves * kRfRows;

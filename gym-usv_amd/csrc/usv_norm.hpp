@@ -13,10 +13,10 @@
 //   2. norm_finalise_kernel  one 64-lane block per column (D obs columns + the returns): combines the
 //      column's partials in block-index order (the fixed tree of usv_norm_math.hpp) and merges the batch
 //      into mean / var.  Every column reads the same old count, so no block of this launch writes it.
-//   3. wrap_step_norm_kernel wrap_step_kernel's work (usv_wrap.hpp: same work split, same ordering
-//      argument, rows 4-B aligned only) with the transform in the push and in the terminal row; also
-//      norm_rew, returns = 0 for done envs, and -- thread 0 of block 0 -- the two counts, which launch 2
-//      could not bump.
+//   3. wrap_step_norm_kernel wrap_step_body (usv_wrap.hpp: wrap_step_kernel's code, so the same work
+//      split and ordering argument) under the WrapNorm policy: the transform in the push and in the
+//      terminal row, norm_rew, returns = 0 for done envs; before it norm_stage: the tables and -- thread 0
+//      of block 0 -- the two counts, which launch 2 could not bump.
 // No block waits for another anywhere; the order between launches is the stream's.
 //
 // Tables.  A lane normalising four floats needs four (mean, inv_std) pairs, 64 B.  Each block stages the
@@ -195,153 +195,50 @@ __device__ __forceinline__ double norm_stage(const NormArgs& z, double* tab) {
   return rinv;
 }
 
-// wrap_push with every float normalised on its way (column c of a piece: pairs c .. c + 3 of tab).
-__device__ __forceinline__ void wrap_push_norm(const WrapArgs& a, const double* tab, double clip, const float* src,
-                                               int e0, int ne, int l) {
-  const int D = a.D;
-  float* const dst = a.ring + (size_t)e0 * a.stride + (size_t)a.p * D;
-  const ptrdiff_t mir = a.m >= 0 ? (ptrdiff_t)(a.m - a.p) * D : 0;
-  const float* const span = src + (size_t)e0 * D;
-  if (D >= 4) {
-    const int P = (D + 3) / 4, np = ne * P;
-    const int dk = kWave / P, dr = kWave % P;
-    int k = l / P, r = l - k * P;
-    for (int q = l; q < np; q += 3 * kWave) {
-      const float* sp[3];
-      float* dp[3];
-      int cc[3];
-      WrapQuad4 v[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int c = min(4 * r, D - 4);
-        cc[i] = c;
-        sp[i] = span + k * D + c;
-        dp[i] = dst + (size_t)k * a.stride + c;
-        k += dk;
-        r += dr;
-        if (r >= P) { r -= P; ++k; }
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (q + i * kWave < np) v[i] = *reinterpret_cast<const WrapQuad*>(sp[i]);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (q + i * kWave < np) {
-          const double* const t = tab + 2 * cc[i];
-          WrapQuad4 o;
-          o.x = norm_apply((double)v[i].x, t[0], t[1], clip);
-          o.y = norm_apply((double)v[i].y, t[2], t[3], clip);
-          o.z = norm_apply((double)v[i].z, t[4], t[5], clip);
-          o.w = norm_apply((double)v[i].w, t[6], t[7], clip);
-          *reinterpret_cast<WrapQuad*>(dp[i]) = o;
-          if (a.m >= 0) *reinterpret_cast<WrapQuad*>(dp[i] + mir) = o;
-        }
-    }
-  } else {
-    const int nd = ne * D;
-    for (int q = l; q < nd; q += kWave) {
-      const int k = q / D, c = q - k * D;
-      const float v = norm_apply((double)span[q], tab[2 * c], tab[2 * c + 1], clip);
-      float* const d = dst + (size_t)k * a.stride + c;
-      d[0] = v;
-      if (a.m >= 0) d[mir] = v;
-    }
+// The wrappers' normalisation policy (usv_wrap.hpp).  NORM_OBS: every frame float is normalised on its
+// way (column c of a piece: pairs c .. c + 3 of tab); the reward's switch is z.norm_rew.  norm_rew: the
+// step's normalised-reward output (null in a reset).
+template <bool NORM_OBS>
+struct WrapNorm {
+  const NormArgs& z;
+  const double* tab;
+  double rinv;
+  float* norm_rew;
+  template <typename RW>
+  __device__ __forceinline__ void reward(int e, RW rw) const {
+    norm_rew[e] = z.norm_rew ? norm_apply((double)rw, 0.0, rinv, z.clip_rew) : (float)rw;
   }
-}
+  __device__ __forceinline__ void restart(int e) const { z.returns[e] = 0.0; }
+  __device__ __forceinline__ float one(float v, int c) const {
+    return NORM_OBS ? norm_apply((double)v, tab[2 * c], tab[2 * c + 1], z.clip_obs) : v;
+  }
+  __device__ __forceinline__ WrapQuad4 quad(WrapQuad4 v, int c) const {
+    if (!NORM_OBS) return v;
+    const double* const t = tab + 2 * c;
+    WrapQuad4 o;
+    o.x = norm_apply((double)v.x, t[0], t[1], z.clip_obs);
+    o.y = norm_apply((double)v.y, t[2], t[3], z.clip_obs);
+    o.z = norm_apply((double)v.z, t[4], t[5], z.clip_obs);
+    o.w = norm_apply((double)v.w, t[6], t[7], z.clip_obs);
+    return o;
+  }
+};
 
-// wrap_step_kernel with the normalisation (NORM_OBS: of the frames; the reward's by z.norm_rew).
 template <typename RW, bool NORM_OBS>
 __global__ __launch_bounds__(kBlock) void wrap_step_norm_kernel(WrapArgs a, NormArgs z, const float* obs, const RW* rew,
                                                                const uint8_t* done, const float* final_obs,
                                                                float* final_stack, float* norm_rew) {
   extern __shared__ double norm_tab[];
   const double rinv = norm_stage<NORM_OBS>(z, norm_tab);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int l = lane_id();
-  const int e0 = (blockIdx.x * kWaves + wave) * kWrapEnvs;
-  const int ne = min(kWrapEnvs, a.n - e0);
-  if (ne <= 0) return;
-  // ---- stats (the raw reward: the Monitor sits inside VecNormalize), the normalised reward
-  bool dn = false;
-  if (l < ne) {
-    const int e = e0 + l;
-    const RW rw = rew[e];
-    double ret = a.ep_ret[e] + (double)rw;
-    int len = a.ep_len[e] + 1;
-    dn = done[e] != 0;
-    norm_rew[e] = z.norm_rew ? norm_apply((double)rw, 0.0, rinv, z.clip_rew) : (float)rw;
-    if (dn) {
-      if (a.episode) {
-        a.episode[2 * (size_t)e] = ret;
-        a.episode[2 * (size_t)e + 1] = (double)len;
-      }
-      if (a.cum_ret) {
-        a.cum_ret[e] += ret;
-        a.cum_len[e] += len;
-        a.cum_eps[e] += 1;
-      }
-      ret = 0.0;
-      len = 0;
-      z.returns[e] = 0.0;
-    }
-    a.ep_ret[e] = ret;
-    a.ep_len[e] = len;
-  }
-  // ---- rare: done envs (terminal stack with the normalised final obs last, then the clear)
-  unsigned long long dm = ballot(dn);
-  if (__builtin_expect(dm != 0ull, 0)) {
-    const int D = a.D, older = (a.k - 1) * D;
-    for (; dm; dm &= dm - 1) {
-      const int e = e0 + __builtin_ctzll(dm);
-      float* const row = a.ring + (size_t)e * a.stride;
-      if (final_stack) {
-        float* const f = final_stack + (size_t)e * a.k * D;
-        const float* const t = row + (size_t)a.term * D;
-        for (int c = l; c < older; c += kWave) f[c] = t[c];
-        const float* const fo = final_obs + (size_t)e * D;
-        for (int c = l; c < D; c += kWave)
-          f[older + c] = NORM_OBS ? norm_apply((double)fo[c], norm_tab[2 * c], norm_tab[2 * c + 1], z.clip_obs) : fo[c];
-        // the loads of the row have returned before the first zero below is issued
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      if (a.keep_sign) wrap_clear_row<true>(row, a, l); else wrap_clear_row<false>(row, a, l);
-    }
-  }
-  // ---- push
-  if (NORM_OBS) wrap_push_norm(a, norm_tab, z.clip_obs, obs, e0, ne, l);
-  else wrap_push(a, obs, e0, ne, l);
+  wrap_step_body(a, obs, rew, done, final_obs, final_stack, WrapNorm<NORM_OBS>{z, norm_tab, rinv, norm_rew});
 }
 
-// wrap_reset_kernel with returns = 0 for the restarted envs and the normalised push.
 template <bool MASKED, bool NORM_OBS>
 __global__ __launch_bounds__(kBlock) void wrap_reset_norm_kernel(WrapArgs a, NormArgs z, const uint8_t* mask,
                                                                 const float* obs) {
   extern __shared__ double norm_tab[];
-  norm_stage<NORM_OBS>(z, norm_tab);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int l = lane_id();
-  const int e0 = (blockIdx.x * kWaves + wave) * kWrapEnvs;
-  const int ne = min(kWrapEnvs, a.n - e0);
-  if (ne <= 0) return;
-  bool on = false;
-  if (l < ne) {
-    on = !MASKED || mask[e0 + l] != 0;
-    if (on) {
-      a.ep_ret[e0 + l] = 0.0;
-      a.ep_len[e0 + l] = 0;
-      z.returns[e0 + l] = 0.0;
-    }
-  }
-  const unsigned long long rm = ballot(on);
-  if (rm == 0ull) return;
-  for (unsigned long long b = rm; b; b &= b - 1)
-    wrap_clear_row<false>(a.ring + (size_t)(e0 + __builtin_ctzll(b)) * a.stride, a, l);
-  const bool all = rm == (ne == 64 ? ~0ull : (1ull << ne) - 1);
-  for (unsigned long long b = all ? 1ull : rm; b; b &= b - 1) {
-    const int f = all ? 0 : __builtin_ctzll(b), cnt = all ? ne : 1;   // every env of the wave, or one row at a time
-    if (NORM_OBS) wrap_push_norm(a, norm_tab, z.clip_obs, obs, e0 + f, cnt, l);
-    else wrap_push(a, obs, e0 + f, cnt, l);
-  }
+  const double rinv = norm_stage<NORM_OBS>(z, norm_tab);
+  wrap_reset_body<MASKED>(a, mask, obs, WrapNorm<NORM_OBS>{z, norm_tab, rinv, nullptr});
 }
 
 }  // namespace usv

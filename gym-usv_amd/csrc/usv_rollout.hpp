@@ -3,11 +3,9 @@
 // without a host sync: usv_rollout_put_obs / _put_step / _gae (include/usv_hip.h).  The arithmetic and
 // the slot numbering are usv_rollout_math.hpp's.
 //
-//   rollout_obs_kernel    row t of obs / act / val / logp.  The obs rows are wrap_push's copy (usv_wrap.hpp)
-//                         with a strided source: a wave owns kWrapEnvs = 16 envs, a row is cut into 16-B
-//                         pieces at declared 4-B alignment, the last piece moved back to end with the row,
-//                         three pieces per lane in flight.  WT: the 16-B stores are write-through (sc1,
-//                         usv_noscan_step.hpp's st_obs4).
+//   rollout_obs_kernel    row t of obs / act / val / logp (rollout_put_rows).  A wave owns kWrapEnvs = 16
+//                         envs; their obs rows are copy_rows's (usv_row_copy.hpp) from a strided source,
+//                         plain stores.
 //   rollout_count_kernel  one block per chunk of envs: counts[b] = the chunk's bootstrapping envs.
 //   rollout_step_kernel   one block per chunk: rew[t], start[t + 1], term_slot[t] and the rare W-float row
 //                         copy into term_obs, by the whole wave.  Every block sums the <= 1024 chunk counts
@@ -22,15 +20,11 @@
 #pragma once
 
 #include "usv_rollout_math.hpp"
-#include "usv_noscan_step.hpp"
-#include "usv_wrap.hpp"
+#include "usv_row_copy.hpp"
 
 namespace usv {
 
 static_assert(kRoBlock == kBlock, "usv_rollout_math.hpp's chunk pass is this block");
-
-// The obs store's policy ("Device rollout buffer": measured both ways).
-constexpr bool kRolloutStoreWt = false;
 
 struct RoArgs {
   int n, T, W, A, cap;
@@ -49,15 +43,11 @@ struct RoArgs {
   int32_t* counts;
 };
 
-template <bool WT>
-__device__ __forceinline__ void ro_store4(float* p, WrapQuad4 v) {
-  if (WT) st_obs4(p, v);
-  else *reinterpret_cast<WrapQuad*>(p) = v;
-}
-
-template <bool WT>
-__global__ __launch_bounds__(kBlock) void rollout_obs_kernel(RoArgs a, int t, const float* src, size_t sstride,
-                                                            const float* act, const float* val, const float* logp) {
+// Row t of val / logp / act, and W floats of each env's src row (stride sstride) into dst + e * dstride:
+// what the two put_obs kernels do for a wave.
+__device__ __forceinline__ void rollout_put_rows(const RoArgs& a, int t, const float* src, size_t sstride, float* dst,
+                                                 size_t dstride, int W, const float* act, const float* val,
+                                                 const float* logp) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int l = lane_id();
   const int e0 = (blockIdx.x * kWaves + wave) * kWrapEnvs;
@@ -69,39 +59,13 @@ __global__ __launch_bounds__(kBlock) void rollout_obs_kernel(RoArgs a, int t, co
     a.logp[row0 + l] = logp[e0 + l];
   }
   for (int q = l; q < ne * a.A; q += kWave) a.act[row0 * a.A + q] = act[(size_t)e0 * a.A + q];
-  const int W = a.W;
-  const float* const span = src + (size_t)e0 * sstride;
-  float* const dst = a.obs + row0 * W;
-  if (W >= 4) {
-    const int P = (W + 3) / 4, np = ne * P;             // pieces per row, of the wave
-    const int dk = kWave / P, dr = kWave % P;
-    int k = l / P, r = l - k * P;                       // piece l + 64 i: row k, piece r of it
-    for (int q = l; q < np; q += 3 * kWave) {
-      const float* sp[3];
-      float* dp[3];
-      WrapQuad4 v[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int c = min(4 * r, W - 4);
-        sp[i] = span + (size_t)k * sstride + c;
-        dp[i] = dst + (size_t)k * W + c;
-        k += dk;
-        r += dr;
-        if (r >= P) { r -= P; ++k; }
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (q + i * kWave < np) v[i] = *reinterpret_cast<const WrapQuad*>(sp[i]);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (q + i * kWave < np) ro_store4<WT>(dp[i], v[i]);
-    }
-  } else {
-    for (int q = l; q < ne * W; q += kWave) {
-      const int k = q / W, c = q - k * W;
-      dst[q] = span[(size_t)k * sstride + c];
-    }
-  }
+  copy_rows(src + (size_t)e0 * sstride, sstride, dst + (size_t)e0 * dstride, dstride, false, 0, W, ne, l,
+            RowCopyPlain{});
+}
+
+__global__ __launch_bounds__(kBlock) void rollout_obs_kernel(RoArgs a, int t, const float* src, size_t sstride,
+                                                            const float* act, const float* val, const float* logp) {
+  rollout_put_rows(a, t, src, sstride, a.obs + (size_t)t * a.n * a.W, (size_t)a.W, a.W, act, val, logp);
 }
 
 __global__ __launch_bounds__(kBlock) void rollout_count_kernel(RoArgs a, const uint8_t* term, const uint8_t* trunc) {

@@ -3,12 +3,10 @@
 // usv_rollout_gather (include/usv_hip.h).  The layout, the live mask and the clear rule are
 // usv_rollout_frames_math.hpp's.
 //
-//   rollout_frames_obs_kernel  rollout_obs_kernel (usv_rollout.hpp) with a destination row stride: row t
-//                              of act / val / logp, and of each env's window the columns that are new --
-//                              all k D at t = 0 (frame rows 0 .. k - 1), the newest D afterwards (frame
-//                              row t + k - 1).  A wave owns kWrapEnvs = 16 envs; a row is cut into 16-B
-//                              pieces at declared 4-B alignment, the last piece moved back to end with
-//                              the row, three pieces per lane in flight, plain stores.
+//   rollout_frames_obs_kernel  rollout_obs_kernel's work (rollout_put_rows, usv_rollout.hpp) with a
+//                              destination row stride: row t of act / val / logp, and of each env's window
+//                              the columns that are new -- all k D at t = 0 (frame rows 0 .. k - 1), the
+//                              newest D afterwards (frame row t + k - 1).
 //   rollout_gather_kernel      a wave owns kRfRows = 4 consecutive samples.  Lane r < 4 reads idx[b0 + r],
 //                              checks it, splits it into (t, e), builds the live mask from at most k - 1
 //                              start bytes and moves the four scalars; the offsets and masks are then
@@ -38,51 +36,9 @@ struct RfArgs {
 __global__ __launch_bounds__(kBlock) void rollout_frames_obs_kernel(RoArgs a, RfArgs f, int t, const float* src,
                                                                    size_t sstride, const float* act, const float* val,
                                                                    const float* logp) {
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int l = lane_id();
-  const int e0 = (blockIdx.x * kWaves + wave) * kWrapEnvs;
-  const int ne = min(kWrapEnvs, a.n - e0);
-  if (ne <= 0) return;
-  const size_t row0 = (size_t)t * a.n + e0;             // first of the wave's rows in a [T][n] buffer
-  if (l < ne) {
-    a.val[row0 + l] = val[e0 + l];
-    a.logp[row0 + l] = logp[e0 + l];
-  }
-  for (int q = l; q < ne * a.A; q += kWave) a.act[row0 * a.A + q] = act[(size_t)e0 * a.A + q];
-  const int W = rf_put_width(t, f.k, f.D);              // the columns of the window that are new
-  const size_t dstride = (size_t)rf_rows(a.T, f.k) * f.D;
-  const float* const span = src + (size_t)e0 * sstride + rf_put_col(t, f.k, f.D);
-  float* const dst = f.frames + rf_row_offset(e0, rf_put_row(t, f.k), a.T, f.k, f.D);
-  if (W >= 4) {
-    const int P = (W + 3) / 4, np = ne * P;             // pieces per row, of the wave
-    const int dk = kWave / P, dr = kWave % P;
-    int k = l / P, r = l - k * P;                       // piece l + 64 i: row k, piece r of it
-    for (int q = l; q < np; q += 3 * kWave) {
-      const float* sp[3];
-      float* dp[3];
-      WrapQuad4 v[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int c = min(4 * r, W - 4);
-        sp[i] = span + (size_t)k * sstride + c;
-        dp[i] = dst + (size_t)k * dstride + c;
-        k += dk;
-        r += dr;
-        if (r >= P) { r -= P; ++k; }
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (q + i * kWave < np) v[i] = *reinterpret_cast<const WrapQuad*>(sp[i]);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (q + i * kWave < np) *reinterpret_cast<WrapQuad*>(dp[i]) = v[i];
-    }
-  } else {
-    for (int q = l; q < ne * W; q += kWave) {
-      const int k = q / W, c = q - k * W;
-      dst[(size_t)k * dstride + c] = span[(size_t)k * sstride + c];
-    }
-  }
+  rollout_put_rows(a, t, src + rf_put_col(t, f.k, f.D), sstride,
+                   f.frames + rf_row_offset(0, rf_put_row(t, f.k), a.T, f.k, f.D), (size_t)rf_rows(a.T, f.k) * f.D,
+                   rf_put_width(t, f.k, f.D), act, val, logp);
 }
 
 __global__ __launch_bounds__(kBlock) void rollout_gather_kernel(RoArgs a, RfArgs f, const int64_t* idx, int B,

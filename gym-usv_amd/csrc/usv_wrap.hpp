@@ -15,15 +15,12 @@
 //           accesses.
 //   rare    a done env (about 1 in 216 per step): the whole wave copies its terminal stack and zeroes
 //           its older frames (+0.0, or x * 0 with USV_WRAP_CLEAR_KEEPS_SIGN: wrap_clear_row).
-//   push    the wave's 16 obs rows are one contiguous source span.  It is cut into pieces of four
-//           floats per row, ceil(D / 4) pieces each, the last one moved back to end with the row (it
-//           re-copies up to three floats of its neighbour: the same values from the same wave).  Lane l
-//           takes pieces l, l + 64, ...: one 16-B load and one or two 16-B stores each, 1 KiB of
-//           contiguous source per wave instruction; D = 143: 9 pieces per lane, three in flight.
-//           Rows are 4-B aligned in general (143 floats = 572 B), and the accesses are declared so: a
-//           16-B global access needs dword alignment only, and is full rate when the address happens
-//           to be 16-B aligned.
-//           D < 4 takes one float per piece.
+//   push    the wave's 16 obs rows are one contiguous source span, copied into the ring slots of frame j
+//           by copy_rows (usv_row_copy.hpp: 16-B pieces at declared 4-B alignment, three in flight).
+//
+// The step and the reset are one body each (wrap_step_body, wrap_reset_body) over a normalisation
+// policy: WrapNoNorm here, WrapNorm of usv_norm.hpp for VecNormalize.  The policy is also the copy's
+// transform.  The plain kernels' policy is empty: they take no NormArgs, no LDS and no barrier.
 //
 // Ordering within an env's ring row (the argument of usv_noscan_step.hpp for its obs span): all
 // accesses to the row in a launch come from the wave that owns the env, and launches on a stream are
@@ -35,11 +32,9 @@
 #pragma once
 
 #include "usv_wrap_layout.hpp"
-#include "usv_state.hpp"
+#include "usv_row_copy.hpp"
 
 namespace usv {
-
-constexpr int kWrapEnvs = 16;   // envs per wave: 4 096 waves at 65 536 envs, each moving ~27 KB
 
 struct WrapArgs {
   int n, D, k, reward_bytes;
@@ -55,9 +50,12 @@ struct WrapArgs {
   long long* cum_eps;
 };
 
-// four floats at dword alignment: one global_load / global_store_dwordx4
-typedef float WrapQuad4 __attribute__((ext_vector_type(4)));
-typedef WrapQuad4 WrapQuad __attribute__((aligned(4)));
+// No normalisation: nothing besides the wrappers' own work, and the frames are stored as they are.
+struct WrapNoNorm : RowCopyPlain {
+  template <typename RW>
+  __device__ __forceinline__ void reward(int, RW) const {}   // env e's raw reward of this step
+  __device__ __forceinline__ void restart(int) const {}      // env e starts an episode
+};
 
 // Zero every slot of a ring row but those of frame j (wrap_clears_slot), the whole wave.  KEEP_SIGN:
 // x * 0 instead of +0.0, i.e. -0.0 where x was negative, as a stack cleared by a mask multiply holds
@@ -73,69 +71,33 @@ __device__ __forceinline__ void wrap_clear_row(float* row, const WrapArgs& a, in
 }
 
 // Frame j of the wave's `ne` envs from src rows (row stride D) into the ring slots p and m.
-__device__ __forceinline__ void wrap_push(const WrapArgs& a, const float* src, int e0, int ne, int l) {
+template <typename NORM>
+__device__ __forceinline__ void wrap_push(const WrapArgs& a, const float* src, int e0, int ne, int l, const NORM& nz) {
   const int D = a.D;
   float* const dst = a.ring + (size_t)e0 * a.stride + (size_t)a.p * D;
   const ptrdiff_t mir = a.m >= 0 ? (ptrdiff_t)(a.m - a.p) * D : 0;
-  const float* const span = src + (size_t)e0 * D;
-  if (D >= 4) {
-    const int P = (D + 3) / 4, np = ne * P;             // pieces per row, of the wave
-    const int dk = kWave / P, dr = kWave % P;
-    int k = l / P, r = l - k * P;                       // piece l + 64 i: row k, piece r of it
-    // three pieces per pass: their loads are in flight together
-    for (int q = l; q < np; q += 3 * kWave) {
-      const float* sp[3];
-      float* dp[3];
-      WrapQuad4 v[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int c = min(4 * r, D - 4);
-        sp[i] = span + k * D + c;
-        dp[i] = dst + (size_t)k * a.stride + c;
-        k += dk;
-        r += dr;
-        if (r >= P) { r -= P; ++k; }
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (q + i * kWave < np) v[i] = *reinterpret_cast<const WrapQuad*>(sp[i]);
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-        if (q + i * kWave < np) {
-          *reinterpret_cast<WrapQuad*>(dp[i]) = v[i];
-          if (a.m >= 0) *reinterpret_cast<WrapQuad*>(dp[i] + mir) = v[i];
-        }
-    }
-  } else {
-    const int nd = ne * D;
-    for (int q = l; q < nd; q += kWave) {
-      const int k = q / D, c = q - k * D;
-      const float v = span[q];
-      float* const d = dst + (size_t)k * a.stride + c;
-      d[0] = v;
-      if (a.m >= 0) d[mir] = v;
-    }
-  }
+  copy_rows(src + (size_t)e0 * D, D, dst, a.stride, a.m >= 0, mir, D, ne, l, nz);
 }
 
-// obs / rew / done / final_obs: what usv_step wrote; final_stack [n][k D] or null.
+// The step of a wave.  obs / rew / done / final_obs: what usv_step wrote; final_stack [n][k D] or null.
 // RW: the reward's type (reward_bytes).
-template <typename RW>
-__global__ __launch_bounds__(kBlock) void wrap_step_kernel(WrapArgs a, const float* obs, const RW* rew,
-                                                          const uint8_t* done, const float* final_obs,
-                                                          float* final_stack) {
+template <typename RW, typename NORM>
+__device__ __forceinline__ void wrap_step_body(const WrapArgs& a, const float* obs, const RW* rew, const uint8_t* done,
+                                               const float* final_obs, float* final_stack, const NORM& nz) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int l = lane_id();
   const int e0 = (blockIdx.x * kWaves + wave) * kWrapEnvs;   // this wave's envs: e0 .. e0 + ne - 1
   const int ne = min(kWrapEnvs, a.n - e0);
   if (ne <= 0) return;
-  // ---- stats
+  // ---- stats (of the raw reward: the Monitor sits inside VecNormalize)
   bool dn = false;
   if (l < ne) {
     const int e = e0 + l;
-    double ret = a.ep_ret[e] + (double)rew[e];
+    const RW rw = rew[e];
+    double ret = a.ep_ret[e] + (double)rw;
     int len = a.ep_len[e] + 1;
     dn = done[e] != 0;
+    nz.reward(e, rw);
     if (dn) {
       if (a.episode) {
         a.episode[2 * (size_t)e] = ret;
@@ -148,11 +110,12 @@ __global__ __launch_bounds__(kBlock) void wrap_step_kernel(WrapArgs a, const flo
       }
       ret = 0.0;
       len = 0;
+      nz.restart(e);
     }
     a.ep_ret[e] = ret;
     a.ep_len[e] = len;
   }
-  // ---- rare: done envs (terminal stack, then the clear)
+  // ---- rare: done envs (terminal stack with the final obs last, then the clear)
   unsigned long long dm = ballot(dn);
   if (__builtin_expect(dm != 0ull, 0)) {
     const int D = a.D, older = (a.k - 1) * D;
@@ -164,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void wrap_step_kernel(WrapArgs a, const flo
         const float* const t = row + (size_t)a.term * D;   // frames j-k+1 .. j-1
         for (int c = l; c < older; c += kWave) f[c] = t[c];
         const float* const fo = final_obs + (size_t)e * D;
-        for (int c = l; c < D; c += kWave) f[older + c] = fo[c];
+        for (int c = l; c < D; c += kWave) f[older + c] = nz.one(fo[c], c);
         // the loads of the row have returned before the first zero below is issued
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
@@ -172,13 +135,13 @@ __global__ __launch_bounds__(kBlock) void wrap_step_kernel(WrapArgs a, const flo
     }
   }
   // ---- push
-  wrap_push(a, obs, e0, ne, l);
+  wrap_push(a, obs, e0, ne, l, nz);
 }
 
-// Envs whose mask byte is set (null: all) restart at frame j: older frames zero, obs as frame j,
-// counters 0.  Same work split as the step.  MASKED = false: mask is null.
-template <bool MASKED>
-__global__ __launch_bounds__(kBlock) void wrap_reset_kernel(WrapArgs a, const uint8_t* mask, const float* obs) {
+// The reset of a wave: envs whose mask byte is set (MASKED = false: mask is null, all) restart at frame
+// j: older frames zero, obs as frame j, counters 0.  Same work split as the step.
+template <bool MASKED, typename NORM>
+__device__ __forceinline__ void wrap_reset_body(const WrapArgs& a, const uint8_t* mask, const float* obs, const NORM& nz) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int l = lane_id();
   const int e0 = (blockIdx.x * kWaves + wave) * kWrapEnvs;
@@ -190,18 +153,30 @@ __global__ __launch_bounds__(kBlock) void wrap_reset_kernel(WrapArgs a, const ui
     if (on) {
       a.ep_ret[e0 + l] = 0.0;
       a.ep_len[e0 + l] = 0;
+      nz.restart(e0 + l);
     }
   }
   const unsigned long long rm = ballot(on);
   if (rm == 0ull) return;
   for (unsigned long long b = rm; b; b &= b - 1)
     wrap_clear_row<false>(a.ring + (size_t)(e0 + __builtin_ctzll(b)) * a.stride, a, l);
-  if (rm == (ne == 64 ? ~0ull : (1ull << ne) - 1)) {
-    wrap_push(a, obs, e0, ne, l);                       // every env of the wave
-  } else {
-    for (unsigned long long b = rm; b; b &= b - 1)      // one row at a time
-      wrap_push(a, obs, e0 + __builtin_ctzll(b), 1, l);
+  const bool all = rm == (ne == 64 ? ~0ull : (1ull << ne) - 1);
+  for (unsigned long long b = all ? 1ull : rm; b; b &= b - 1) {
+    const int f = all ? 0 : __builtin_ctzll(b), cnt = all ? ne : 1;   // every env of the wave, or one row at a time
+    wrap_push(a, obs, e0 + f, cnt, l, nz);
   }
+}
+
+template <typename RW>
+__global__ __launch_bounds__(kBlock) void wrap_step_kernel(WrapArgs a, const float* obs, const RW* rew,
+                                                          const uint8_t* done, const float* final_obs,
+                                                          float* final_stack) {
+  wrap_step_body(a, obs, rew, done, final_obs, final_stack, WrapNoNorm{});
+}
+
+template <bool MASKED>
+__global__ __launch_bounds__(kBlock) void wrap_reset_kernel(WrapArgs a, const uint8_t* mask, const float* obs) {
+  wrap_reset_body<MASKED>(a, mask, obs, WrapNoNorm{});
 }
 
 }  // namespace usv

@@ -189,3 +189,28 @@ def check(rc, lib=None):
         msg = (lib or load()).usv_last_error().decode(errors="replace")
         raise UsvLibError(f"libusvhip error {rc}: {msg}")
     return rc
+
+
+# ---- what the classes over device tensors share (torch is theirs to import: this module stays ctypes-only)
+def ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def stream_ptr(device):
+    """The current stream of ``device`` as the ``void* stream`` of the C entries."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def cuda_device(device, who):
+    """``device`` (a torch.device, a string or a GPU index) as a torch.device; ``who`` has no CPU fallback."""
+    import torch
+    device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+    if device.type != "cuda":
+        raise UsvLibError(f"{who} runs on a ROCm GPU only (no CPU fallback)")
+    return device
+
+
+def check_tensor(name, t, dtype, shape, device):
+    if t.dtype != dtype or tuple(t.shape) != shape or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {device}")

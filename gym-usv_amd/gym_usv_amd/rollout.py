@@ -38,10 +38,7 @@ import ctypes
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+from ._lib import ptr as _ptr
 
 
 # The fields of SB3's RolloutBufferSamples (common/type_aliases.py), in its order.
@@ -93,9 +90,7 @@ class DeviceRollout:
             raise ValueError("term_cap must be >= 0")
         if reward_dtype not in (torch.float32, torch.float64):
             raise ValueError("reward_dtype must be torch.float32 or torch.float64")
-        device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
-        if device.type != "cuda":
-            raise _lib.UsvLibError("DeviceRollout runs on a ROCm GPU only (no CPU fallback)")
+        device = _lib.cuda_device(device, "DeviceRollout")
         self.lib = _lib.load(lib_path)
         self.n, self.n_steps, self.w, self.a, self.term_cap = n, T, W, A, cap
         self.device, self.reward_dtype = device, reward_dtype
@@ -131,8 +126,7 @@ class DeviceRollout:
         self._fp = ctypes.byref(self._fr)
 
     def _check(self, name, t, dtype, shape):
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        _lib.check_tensor(name, t, dtype, shape, self.device)
 
     def _check_t(self, t):
         if not 0 <= int(t) < self.n_steps:
@@ -140,7 +134,7 @@ class DeviceRollout:
         return int(t)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_ptr(self.device)
 
     def put_obs(self, t, obs, act, val, logp):
         """Row ``t`` of ``obs`` / ``act`` / ``val`` / ``logp``: the observation the action was computed

@@ -28,10 +28,7 @@ import dataclasses
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+from ._lib import ptr as _ptr
 
 
 @dataclasses.dataclass
@@ -89,9 +86,7 @@ class DeviceWrappers:
     def __init__(self, num_envs, obs_dim, n_stack, device, reward_dtype=torch.float32, lib_path=None,
                  clear_keeps_sign=False, normalize=None):
         self._cfg = NormalizeConfig.of(normalize) if normalize is not None else None
-        device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
-        if device.type != "cuda":
-            raise _lib.UsvLibError("DeviceWrappers runs on a ROCm GPU only (no CPU fallback)")
+        device = _lib.cuda_device(device, "DeviceWrappers")
         if reward_dtype not in (torch.float32, torch.float64):
             raise ValueError("reward_dtype must be torch.float32 or torch.float64")
         self.lib = _lib.load(lib_path)
@@ -152,11 +147,10 @@ class DeviceWrappers:
                          _lib.NORM_REWARD * bool(self.norm_reward))
 
     def _check_rows(self, name, t, dtype, shape):
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        _lib.check_tensor(name, t, dtype, shape, self.device)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_ptr(self.device)
 
     @property
     def stacked(self):
@@ -174,10 +168,10 @@ class DeviceWrappers:
             self._check_rows("mask", mask, mask.dtype, (self.n,))
         if self._cfg is not None:
             self._norm_flags()
-            _lib.check(self.lib.usv_wrap_reset_norm(self._wp, self._zp, self._j, _ptr(mask), _ptr(obs), self._stream()),
-                       self.lib)
-            return self.stacked
-        _lib.check(self.lib.usv_wrap_reset(self._wp, self._j, _ptr(mask), _ptr(obs), self._stream()), self.lib)
+            rc = self.lib.usv_wrap_reset_norm(self._wp, self._zp, self._j, _ptr(mask), _ptr(obs), self._stream())
+        else:
+            rc = self.lib.usv_wrap_reset(self._wp, self._j, _ptr(mask), _ptr(obs), self._stream())
+        _lib.check(rc, self.lib)
         return self.stacked
 
     def step(self, obs, rew, done, final_obs=None):
@@ -194,16 +188,15 @@ class DeviceWrappers:
         if final_obs is not None:
             self._check_rows("final_obs", final_obs, torch.float32, (n, d))
         j = self._j + 1
+        fs = self._fs_ptr if final_obs is not None else None
         if self._cfg is not None:
             self._norm_flags()
-            _lib.check(self.lib.usv_wrap_step_norm(self._wp, self._zp, j, _ptr(obs), _ptr(rew), _ptr(done),
-                                                   _ptr(final_obs), self._fs_ptr if final_obs is not None else None,
-                                                   self._nr_ptr, self._stream()), self.lib)
-            self._j = j
-            return self.stacked, (self.final_stack if final_obs is not None else None), self.episode
-        _lib.check(self.lib.usv_wrap_step(self._wp, j, _ptr(obs), _ptr(rew), _ptr(done), _ptr(final_obs),
-                                          self._fs_ptr if final_obs is not None else None, self._stream()),
-                   self.lib)
+            rc = self.lib.usv_wrap_step_norm(self._wp, self._zp, j, _ptr(obs), _ptr(rew), _ptr(done), _ptr(final_obs), fs,
+                                             self._nr_ptr, self._stream())
+        else:
+            rc = self.lib.usv_wrap_step(self._wp, j, _ptr(obs), _ptr(rew), _ptr(done), _ptr(final_obs), fs,
+                                        self._stream())
+        _lib.check(rc, self.lib)
         self._j = j
         return self.stacked, (self.final_stack if final_obs is not None else None), self.episode
 

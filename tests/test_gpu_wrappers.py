@@ -113,9 +113,9 @@ def run_scripted(n, d, k, density, rdt, seed, misaligned=False):
         assert eps == n * done.shape[0]
 
 
-@pytest.mark.parametrize("k", [1, 2, 5])
-@pytest.mark.parametrize("d", [143, 6])
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+# d = 3: the row copy's one-float path, with and without the mirror store, and a wave of one env
+@pytest.mark.parametrize("n,d,k", [(n, d, k) for k in (1, 2, 5) for d in (143, 6) for n in (1, 63, 64, 65, 257)] +
+                         [(65, 3, 1), (65, 3, 2)])
 def test_scripted_steps_match_frame_stack_and_torch_stats(n, d, k):
     """3k + 2 steps after a reset; done densities 0, 1 and ~0.1 with repeats; f32 and f64 rewards."""
     for density in (0, 1, 0.1):
@@ -141,8 +141,12 @@ def test_masked_reset_restarts_masked_rows_only():
     """A masked reset of a random half of 257 envs mid-sequence: masked rows restart (zeros + the new
     obs, counters 0) and go on like a wrapper reset in full at that point; the other rows are
     bit-identical to a run without the reset."""
+    for n, d, k in ((257, 143, 5), (65, 3, 1), (65, 3, 2)):     # d = 3: the row copy's one-float path
+        masked_reset(n, d, k, at=4)
+
+
+def masked_reset(n, d, k, at):
     from gym_usv_amd.wrappers import DeviceWrappers
-    n, d, k, at = 257, 143, 5, 4
     dev = torch.device("cuda", 0)
     obs, final, rew, done = (t.to(dev) for t in script(n, d, k, 0.1, torch.float32, seed=11))
     g = torch.Generator().manual_seed(12)

@@ -12,9 +12,8 @@ value function (one Linear) in every leg.  A leg is one whole rollout: T steps, 
                    the clone of the stacked obs, the truncation bookkeeping with its host syncs
                    (bool(trunc.any()), done.nonzero(), bool(tr.any())), the value of the compacted terminal
                    rows, and advantages() -- existing code, the yardstick
-  (b) fused        DeviceRollout.put_obs / put_step per step, one value pass over term_obs, gae; once with
-                   plain 16-B obs stores and once with write-through (sc1) ones (USV_ROLLOUT_STORE)
-  (s) store only   put_obs alone under both policies: its bytes per second against the HBM peak
+  (b) fused        DeviceRollout.put_obs / put_step per step, one value pass over term_obs, gae
+  (s) store only   put_obs alone: its bytes per second against the HBM peak
 at 4 096 envs x T = 32 and 65 536 envs x T = 8.  Per leg: median and min..max over the rounds of the time
 per rollout.  Needs a GPU; there is no fallback.
 
@@ -125,16 +124,15 @@ class TorchLeg:
 
 
 class FusedLeg:
-    """(b), with the store policy in USV_ROLLOUT_STORE for the leg's calls."""
+    """(b)."""
 
-    def __init__(self, torch, n, T, inp, dev, store, n_stack=None):
+    def __init__(self, torch, n, T, inp, dev, n_stack=None):
         from gym_usv_amd.rollout import DeviceRollout
-        self.torch, self.inp, self.T, self.store = torch, inp, T, store
+        self.torch, self.inp, self.T = torch, inp, T
         self.ro = DeviceRollout(n, T, W, A, dev, n_stack=n_stack)
         self.i = 0
 
     def rollout(self):
-        os.environ["USV_ROLLOUT_STORE"] = self.store
         inp, ro = self.inp, self.ro
         with self.torch.no_grad():
             for t in range(self.T):
@@ -142,20 +140,16 @@ class FusedLeg:
                 self.i += 1
                 ro.put_obs(t, inp.window(t), inp.act[i], inp.val[i], inp.logp[i])
                 ro.put_step(t, inp.rew[i], inp.term[i], inp.trunc[i], inp.final)
-            out = ro.gae(inp.value(inp.window(self.T)), inp.value(ro.term_obs), GAMMA, LAM)
-        del os.environ["USV_ROLLOUT_STORE"]
-        return out
+            return ro.gae(inp.value(inp.window(self.T)), inp.value(ro.term_obs), GAMMA, LAM)
 
 
 class StoreLeg(FusedLeg):
     """(s): put_obs alone."""
 
     def rollout(self):
-        os.environ["USV_ROLLOUT_STORE"] = self.store
         inp, ro = self.inp, self.ro
         for t in range(self.T):
             ro.put_obs(t, inp.window(t), inp.act[0], inp.val[0], inp.logp[0])
-        del os.environ["USV_ROLLOUT_STORE"]
 
 
 def gather_bytes_per_sample(w=W, a=A):
@@ -197,10 +191,10 @@ def frames_main(torch, args, dev):
            "peak_bytes_per_s": PEAK, "sizes": {}}
     for n, T, B in ((4096, 32, 4096), (65536, 8, 65536)):
         inp = Inputs(torch, n, 64 if n <= 4096 else 16, dev)
-        legs = {"store_full": StoreLeg(torch, n, T, inp, dev, "plain"),
-                "store_frames": StoreLeg(torch, n, T, inp, dev, "plain", n_stack=K),
-                "fused_full": FusedLeg(torch, n, T, inp, dev, "plain"),
-                "fused_frames": FusedLeg(torch, n, T, inp, dev, "plain", n_stack=K)}
+        legs = {"store_full": StoreLeg(torch, n, T, inp, dev),
+                "store_frames": StoreLeg(torch, n, T, inp, dev, n_stack=K),
+                "fused_full": FusedLeg(torch, n, T, inp, dev),
+                "fused_frames": FusedLeg(torch, n, T, inp, dev, n_stack=K)}
         for k in ("fused_full", "fused_frames"):
             legs[k].rollout()                                             # the buffers the gathers read
         legs["gather_frames"] = GatherLeg(torch, legs["fused_frames"].ro, B, "kernel")
@@ -296,17 +290,13 @@ def main():
         return
     res = {"what": "interleaved same-process A/B, one stream, HIP-event time per rollout (T steps + advantages): "
                    "torch = examples/ppo_torch.py's buffer stores, truncation bookkeeping with host syncs and "
-                   "advantages(); fused_plain / fused_wt = DeviceRollout with plain / write-through obs stores; "
-                   "store_plain / store_wt = put_obs alone",
+                   "advantages(); fused = DeviceRollout; store = put_obs alone",
            "device": torch.cuda.get_device_name(0), "rounds": args.rounds, "rollouts_per_round": args.reps,
            "n_stack": K, "obs_dim": D, "act_dim": A, "done_rate": DONE_RATE, "peak_bytes_per_s": PEAK, "sizes": {}}
     for n, T in ((4096, 32), (65536, 8)):
         inp = Inputs(torch, n, 64 if n <= 4096 else 16, dev)
-        legs = {"torch": TorchLeg(torch, n, T, inp, dev),
-                "fused_plain": FusedLeg(torch, n, T, inp, dev, "plain"),
-                "fused_wt": FusedLeg(torch, n, T, inp, dev, "wt")}
-        legs["store_plain"] = StoreLeg(torch, n, T, inp, dev, "plain")
-        legs["store_wt"] = StoreLeg(torch, n, T, inp, dev, "wt")
+        legs = {"torch": TorchLeg(torch, n, T, inp, dev), "fused": FusedLeg(torch, n, T, inp, dev),
+                "store": StoreLeg(torch, n, T, inp, dev)}
         for leg in legs.values():
             run_events(torch, leg, args.warmup)
         ev = {k: [] for k in legs}
@@ -316,14 +306,12 @@ def main():
         entry = {k: summary(v) for k, v in ev.items()}
         entry["n_steps"] = T
         b = store_bytes_per_env() * n * T
-        for k in ("store_plain", "store_wt"):
-            rate = b / (entry[k]["median_us"] * 1e-6)
-            entry[k]["bytes_per_rollout"] = b
-            entry[k]["achieved_bytes_per_s"] = round(rate, 1)
-            entry[k]["hbm_peak_frac"] = round(rate / PEAK, 4)
-        for k in ("fused_plain", "fused_wt"):
-            entry[k]["torch_over_this_median"] = round(entry["torch"]["median_us"] / entry[k]["median_us"], 2)
-            entry[k]["max_below_torch_min"] = entry[k]["max_us"] < entry["torch"]["min_us"]
+        rate = b / (entry["store"]["median_us"] * 1e-6)
+        entry["store"]["bytes_per_rollout"] = b
+        entry["store"]["achieved_bytes_per_s"] = round(rate, 1)
+        entry["store"]["hbm_peak_frac"] = round(rate / PEAK, 4)
+        entry["fused"]["torch_over_this_median"] = round(entry["torch"]["median_us"] / entry["fused"]["median_us"], 2)
+        entry["fused"]["max_below_torch_min"] = entry["fused"]["max_us"] < entry["torch"]["min_us"]
         res["sizes"][f"{n}x{T}"] = entry
         print(json.dumps({f"{n}x{T}": entry}), flush=True)
         del legs, inp
