@@ -59,6 +59,13 @@ __device__ __forceinline__ R path_ye(R x, R y, R x0, R y0, R x1, R y1) {
   const R inv_len = R(1) / m_sqrt(dx * dx + dy * dy);
   return -(x - x0) * (dy * inv_len) + (y - y0) * (dx * inv_len);
 }
+// ye of a boat on its path start: -0 * sin(a_k) + 0 * cos(a_k), a zero that is negative where the path
+// points into the second quadrant (sin > 0 > cos).  The f64 build returns the reference's zero (a path
+// exactly along -x, dy = +0, is left at +0: the draws do not produce one); the f32 build keeps +0.
+template <typename R> __device__ __forceinline__ R start_ye(R dx, R dy) {
+  if constexpr (std::is_same<R, float>::value) return R(0);
+  else return (dx < R(0) && dy > R(0)) ? R(-0.0) : R(0);
+}
 
 // run_custom_experiment (simple_env.py:292-300): after the usual draws of a reset, the drawn
 // obstacles, path and pose are replaced by the experiment's; target, velocity and action limits
@@ -186,14 +193,15 @@ __device__ __forceinline__ void reset_wave_ep(const State<R>& S, int e, int ep, 
     S.I(I_EPISODE)[e] = ep + 1;
     S.I(I_SCAN)[e] = 0;
     // reset obs: _get_obs(zeros(3)) with the random target_position (:302, :72-80); position
-    // == path_start, so ye == 0 exactly
+    // == path_start, so ye is a zero (start_ye: its sign)
+    const R ye0 = start_ye<R>((sx + ca * dist) - sx, (sy + sa * dist) - sy);
     const R angle = wrap_angle(m_atan2(ty - sy, tx - sx) - psi);
     const R dst = m_hypot(sx - tx, sy - ty);
     float h[kHdr];
-    make_header<R>(h, u, v, r, angle, dst, R(0), refv, R(0), R(0), mu, mr);
+    make_header<R>(h, u, v, r, angle, dst, ye0, refv, R(0), R(0), mu, mr);
 #pragma unroll
     for (int i = 0; i < kHdr; ++i) row[i] = h[i];
-    if (info) reset_info<R>(info, sx, sy, psi, u, v, r, sx, sy, sx + ca * dist, sy + sa * dist, R(0), cdiv(angle, kPi));
+    if (info) reset_info<R>(info, sx, sy, psi, u, v, r, sx, sy, sx + ca * dist, sy + sa * dist, ye0, cdiv(angle, kPi));
   }
 }
 
@@ -360,7 +368,7 @@ __device__ void np_reset(const State<R>& S, int e, float* row, R* info = nullptr
   S.I(I_SCAN)[e] = 0;
   const R angle = wrap_angle(m_atan2(R(ty) - y0, R(tx) - x0) - ps);             // :302, :63-80
   const R dst = m_hypot(x0 - R(tx), y0 - R(ty));
-  const R ye = S.exp ? path_ye(x0, y0, R(ps0), R(ps1), R(pe0), R(pe1)) : R(0);
+  const R ye = S.exp ? path_ye(x0, y0, R(ps0), R(ps1), R(pe0), R(pe1)) : start_ye<R>(R(pe0) - R(ps0), R(pe1) - R(ps1));
   float h[kHdr];
   make_header<R>(h, R(u), R(v), R(r), angle, dst, ye, R(refv), R(0), R(0), R(mu), R(mr));
   for (int i = 0; i < kHdr; ++i) row[i] = h[i];

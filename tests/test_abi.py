@@ -143,8 +143,9 @@ def test_integration_snippet_runs_verbatim_to_create(lib):
 
 def test_div_const_is_ieee_division_on_host(tmp_path):
     """div_const (usv_device.hpp), the f64 build's division by compile-time constants, restated in C with
-    the same fma sequence: equal to x / c for 1e6 random operands per divisor (tools/micro/div_const_check.c;
-    round 6 ran 2e8 per divisor)."""
+    the same fma sequence and select: equal to x / c for 1e6 random operands per divisor with exponents in
+    [-960, 960] and for +-0, +-inf and NaN, and within its derived bound for subnormal and tiny operands
+    (tools/micro/div_const_check.c; round 6 ran 2e8 per divisor)."""
     import os
     import shutil
     import subprocess
@@ -159,3 +160,4 @@ def test_div_const_is_ieee_division_on_host(tmp_path):
     p = subprocess.run([exe, "1000000"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stdout
     assert p.stdout.count(": 0 mismatches") == 10
+    assert p.stdout.count("special values: 0 of 5;") == 10 and p.stdout.count(": 0 of 100000 beyond their bound") == 10

@@ -4,7 +4,9 @@ Tolerances (fp32 kernel vs float64 oracle, state injected so both start identica
   * single step:  obs atol 1e-5 + rtol 1e-4 per element, reward atol 1e-4, flags exact except
     envs whose deciding quantity is within 1e-4 of its threshold; lidar rays whose hit/miss
     decision flips at a grazing ray (|r^2 - perp^2| tiny) <= 1e-4 of rays.
-  * float64 kernel: obs to float32 rounding (atol 2e-6), reward 1e-9.
+  * float64 kernel (usv-simple, usv-asmc-simple): obs equal to the reference's bit for bit, header and
+    sensors; reward 2e-14; no flag mismatch and no collision-threshold flip (DESIGN.md's parity table).
+    The legacy ids keep float32-rounding bounds: the reference's own float32 rounding is in them.
   * golden trajectories (reference-generated): compared up to each env's first episode end.
 """
 import numpy as np
@@ -47,6 +49,22 @@ def to_np(*ts):
     return [t.detach().cpu().numpy() for t in ts]
 
 
+F64_REW_TOL = 2e-14
+# The step's ye multiplies sin / cos of the path angle by the boat's offset from the path start, and the
+# reward's slope in ye is at most 1 / 0.075 (exp(-|ye/k|), exp(-(ye/k)^2), k = 0.075).  Two correctly
+# working routes to that sin / cos (the reference's sin/cos(atan2) in glibc; dy/|d|, dx/|d| or OCML's
+# sin/cos(atan2) in the kernel: both were measured, neither is closer) differ by up to two ulps each, so
+# the f64 reward carries 4 * 2^-53 / 0.075 = 5.9e-15 per metre of |x - x0| + |y - y0| on top of 2e-14.
+# Measured: 1.0e-16 per metre at worst (2.7e-13 at 200 m), 7.1e-15 in all within 20 m of the path start.
+F64_REW_PER_METRE = 4 * 2.0 ** -53 / 0.075
+
+
+def bits_off(a, b):
+    """How many float32 entries differ in their bits (a signed zero or a last-place flip counts)."""
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    return int((a.view(np.uint32) != b.view(np.uint32)).sum())
+
+
 # --------------------------------------------------------------------------- golden replay
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 @pytest.mark.parametrize("fname,env_id", [("simple_traj.npz", "usv-simple"),
@@ -62,14 +80,14 @@ def test_golden_trajectory_replay(golden, fname, env_id, precision):
     env.set_state(golden_state(g))
     alive = np.ones(n, bool)
     worst = {"hdr": 0.0, "rew": 0.0}
-    flips, rays = 0, 0
+    flips, rays, off = 0, 0, 0
     # f32 trajectories accumulate rounding along the rollout (about 5x the measured worst case:
     # usv-simple header 1.4e-6 / reward 1.3e-5; usv-asmc-simple 2.7e-6 / 3.5e-5 since the f32 ASMC
     # integrates the pose with compensated summation -- 1.0e-4 without it, the reward's ye term
     # amplifying a ~50 m float32 position rounded 20 times per step).  The usv-asmc-simple reward
     # tolerance is SURVEY §8(c)'s 1e-4.
     if precision == "f64":
-        hdr_tol, sens_tol, rew_tol = 2e-6, 2e-6, 1e-8
+        hdr_tol, sens_tol, rew_tol = 0.0, 0.0, F64_REW_TOL   # and bit for bit, below
     else:
         hdr_tol, sens_tol, rew_tol = (7e-6, 1e-4, 7e-5) if env_id == "usv-simple" else (1.5e-5, 1e-4, 1e-4)
     for t in range(T):
@@ -82,6 +100,7 @@ def test_golden_trajectory_replay(golden, fname, env_id, precision):
         ref = g["final_obs"][m, t]
         worst["hdr"] = max(worst["hdr"], float(np.abs(obs[m, :15] - ref[:, :15]).max()))
         worst["rew"] = max(worst["rew"], float(np.abs(rew[m] - g["reward"][m, t]).max()))
+        off += bits_off(obs[m], ref)
         # a ray grazing an obstacle edge can flip hit/miss under fp32 rounding: count, bound
         flips += int((np.abs(obs[m, 15:] - ref[:, 15:]) > sens_tol).sum())
         rays += int(m.sum()) * 128
@@ -89,8 +108,9 @@ def test_golden_trajectory_replay(golden, fname, env_id, precision):
         np.testing.assert_array_equal(trunc[m], g["truncated"][m, t], err_msg=f"t={t}")
         alive = alive & ~(g["terminated"][:, t] | g["truncated"][:, t])
     print(f"\n[golden {fname} {precision}] max |hdr| err {worst['hdr']:.3e}, max |rew| err "
-          f"{worst['rew']:.3e}, sensor flips {flips}/{rays}")
+          f"{worst['rew']:.3e}, sensor flips {flips}/{rays}, obs entries not bit-equal {off}")
     assert worst["hdr"] <= hdr_tol and worst["rew"] <= rew_tol, worst
+    assert precision != "f64" or off == 0, off
     assert flips <= (0 if precision == "f64" else max(2, rays // 10000))
     env.close()
 
@@ -124,17 +144,18 @@ def _single_step_round(env_id, n, precision, rounds=4, warm=25, seed=0, scatter=
         g_obs, g_rew, g_term, g_trunc, g_fobs = to_np(obs, rew, term, trunc, info["final_obs"])
         # oracle: same step without its (PCG64) reset, then compare terminal rows
         sens_before = orc.env.sensors.copy()
+        lever = np.abs(orc.env.position[:, :2] - orc.env.path_start).sum(axis=1) + 1.0   # (a step moves < 1 m)
         o_obs, o_rew, o_term, o_trunc, o_fobs, o_done = orc.step(a)
         done = g_term | g_trunc
         stats.append(dict(n=n, term_mis=int((g_term != o_term).sum()), trunc_mis=int((g_trunc != o_trunc).sum()),
                           obs=(g_fobs, g_obs, o_fobs, done & (o_term | o_trunc)),
-                          rew=(g_rew, o_rew), flags_ok=(g_term == o_term) & (g_trunc == o_trunc)))
+                          rew=(g_rew, o_rew), lever=lever, flags_ok=(g_term == o_term) & (g_trunc == o_trunc)))
         del sens_before
     env.close()
     return stats
 
 
-def _check_rows(g_rows, o_rows, atol, rtol, label):
+def _check_rows(g_rows, o_rows, atol, rtol, label, bitwise=False):
     hdr_err = np.abs(g_rows[:, :15] - o_rows[:, :15])
     hdr_bad = hdr_err > atol + rtol * np.abs(o_rows[:, :15])
     sens_err = np.abs(g_rows[:, 15:] - o_rows[:, 15:])
@@ -144,6 +165,8 @@ def _check_rows(g_rows, o_rows, atol, rtol, label):
           f"sensor max err {sens_err.max():.3e}, grazing-ray flips {int(sens_bad.sum())} ({frac:.2e})")
     assert hdr_bad.sum() == 0, f"{label}: header mismatch"
     assert frac <= 1e-4, f"{label}: too many lidar mismatches"
+    if bitwise:
+        assert bits_off(g_rows, o_rows) == 0, f"{label}: {bits_off(g_rows, o_rows)} obs entries not bit-equal"
 
 
 @pytest.mark.parametrize("env_id", ["usv-simple", "usv-asmc-simple"])
@@ -151,13 +174,18 @@ def _check_rows(g_rows, o_rows, atol, rtol, label):
 @pytest.mark.parametrize("scatter", [False, True], ids=["near-start", "scattered"])
 def test_single_step_parity_4096(env_id, precision, scatter):
     """One step from oracle-injected states vs the oracle.  `scattered` spreads the poses over
-    the field so obstacles beyond the 99 m far threshold occur (lidar max-range test)."""
+    the field so obstacles beyond the 99 m far threshold occur (lidar max-range test).
+    f64 asserts DESIGN.md's parity table: obs bit for bit, no flag mismatch, no collision-threshold flip,
+    reward <= 2e-14 plus F64_REW_PER_METRE per metre from the path start (the scattered poses lie up to
+    200 m from it; near the start that term is below 2e-14 and the table's figure is what holds)."""
     n = 4096 if env_id == "usv-simple" else 2048
-    atol, rtol, ratol = (F32_OBS_ATOL, F32_OBS_RTOL, F32_REW_ATOL) if precision == "f32" else (2e-6, 1e-6, 1e-9)
+    atol, rtol, ratol = (F32_OBS_ATOL, F32_OBS_RTOL, F32_REW_ATOL) if precision == "f32" else (0.0, 0.0, F64_REW_TOL)
+    f64 = precision == "f64"
+    flag_slack = 0 if f64 else max(1, n // 2000)          # f64: no flag mismatch, no collision-threshold flip
     # usv-asmc-simple f32 (20 ASMC substeps) holds the same SURVEY §8(c) bounds: r02 measured
     # header 1.7e-6, reward 6.5e-5
     for k, s in enumerate(_single_step_round(env_id, n, precision, scatter=scatter)):
-        assert s["term_mis"] <= max(1, n // 2000) and s["trunc_mis"] <= max(1, n // 2000), s
+        assert s["term_mis"] <= flag_slack and s["trunc_mis"] <= flag_slack, (s["term_mis"], s["trunc_mis"])
         ok = s["flags_ok"]
         g_fobs, g_obs, o_fobs, both_done = s["obs"]
         g_rew, o_rew = s["rew"]
@@ -167,16 +195,18 @@ def test_single_step_parity_4096(env_id, precision, scatter):
         rows = np.flatnonzero(not_done)
         # the oracle vector env resets done envs, so its obs for not-done envs is the step obs
         from_o = o_fobs  # oracle terminal-or-step obs (before any reset)
-        _check_rows(g_obs[rows], from_o[rows], atol, rtol, f"{env_id} {precision} round {k} obs")
+        _check_rows(g_obs[rows], from_o[rows], atol, rtol, f"{env_id} {precision} round {k} obs", f64)
         drows = np.flatnonzero(ok & both_done)
         if drows.size:
-            _check_rows(g_fobs[drows], from_o[drows], atol, rtol, f"{env_id} {precision} round {k} final_obs")
+            _check_rows(g_fobs[drows], from_o[drows], atol, rtol, f"{env_id} {precision} round {k} final_obs", f64)
         rerr = np.abs(g_rew[ok] - o_rew[ok])
         coll_flip = (np.abs(rerr - 20) < 1)       # min sensor within rounding of 0.2
         print(f"[{env_id} {precision} round {k}] reward max err {rerr[~coll_flip].max():.3e}, "
               f"collision-threshold flips {int(coll_flip.sum())}")
-        assert rerr[~coll_flip].max() <= ratol
-        assert coll_flip.sum() <= max(1, n // 2000)
+        tol = ratol + F64_REW_PER_METRE * s["lever"][ok] if f64 else np.full(rerr.shape, ratol)
+        print(f"    reward error over its bound: max {(rerr / tol)[~coll_flip].max():.3f}; lever up to {s['lever'].max():.0f} m")
+        assert (rerr <= tol)[~coll_flip].all()
+        assert coll_flip.sum() <= flag_slack
 
 
 # --------------------------------------------------------------------------- resets
@@ -692,8 +722,8 @@ def test_np_reset_full_trajectory(golden, fname, env_id, precision):
     """reset_rng="numpy": every env draws its resets from its own Generator(PCG64(SeedSequence(
     seed))) in the reference's order (simple_env.py:228-308), so the reference's rollouts replay
     whole, across TimeLimit truncations and terminations with same-step autoreset.
-    f64: the seeded reset state equals the reference's exactly and the full rollout matches at the
-    golden tolerances; f32: the reset state is the reference's rounded to float32."""
+    f64: the seeded reset state equals the reference's exactly and the full rollout matches it bit for
+    bit in every obs row, the sign of a reset row's zero ye included, with the reward within 2e-14; f32: the reset state is the reference's rounded to float32."""
     g = golden(fname)
     n, T = g["actions"].shape[:2]
     limit = int(g["limit"])
@@ -712,12 +742,13 @@ def test_np_reset_full_trajectory(golden, fname, env_id, precision):
         np.testing.assert_array_equal(st[k], want, err_msg=k)
     if precision == "f64":
         np.testing.assert_array_equal(obs, g["obs0"])
+        assert bits_off(obs, g["obs0"]) == 0
     else:
         np.testing.assert_allclose(obs, g["obs0"], atol=2e-6, rtol=0)
         env.close()
         return
     worst = {"obs": 0.0, "fobs": 0.0, "rew": 0.0}
-    resets = 0
+    resets = off = 0
     for t in range(T):
         o, r, te, tr, info = env.step(torch.from_numpy(g["actions"][:, t]).cuda())
         o, r, te, tr, fo = to_np(o, r, te, tr, info["final_obs"])
@@ -727,11 +758,14 @@ def test_np_reset_full_trajectory(golden, fname, env_id, precision):
         resets += int(done.sum())
         worst["obs"] = max(worst["obs"], float(np.abs(o - g["obs"][:, t]).max()))
         worst["rew"] = max(worst["rew"], float(np.abs(r - g["reward"][:, t]).max()))
+        off += bits_off(o, g["obs"][:, t])
         if done.any():
             worst["fobs"] = max(worst["fobs"], float(np.abs(fo[done] - g["final_obs"][done, t]).max()))
-    print(f"\n[np-reset {fname} {env_id}] {resets} in-kernel resets over {n}x{T} steps; max err {worst}")
+            off += bits_off(fo[done], g["final_obs"][done, t])
+    print(f"\n[np-reset {fname} {env_id}] {resets} in-kernel resets over {n}x{T} steps; max err {worst}, "
+          f"obs entries not bit-equal {off}")
     assert resets > 0
-    assert worst["obs"] <= 2e-6 and worst["fobs"] <= 2e-6 and worst["rew"] <= 1e-8, worst
+    assert worst["obs"] == 0 and worst["fobs"] == 0 and worst["rew"] <= F64_REW_TOL and off == 0, (worst, off)
     env.close()
 
 
@@ -742,11 +776,11 @@ def test_np_reset_single_env_api(golden):
     g = golden("simple_traj.npz")
     env = gym_usv_amd.make("usv-simple", precision="f64", reset_rng="numpy")
     obs, _ = env.reset(seed=int(g["seeds"][2]))
-    np.testing.assert_array_equal(obs, g["obs0"][2])
+    assert bits_off(obs, g["obs0"][2]) == 0
     for t in range(40):
         obs, r, te, tr, _ = env.step(g["actions"][2, t])
-        np.testing.assert_array_equal(obs, g["final_obs"][2, t])
-        assert abs(r - g["reward"][2, t]) <= 1e-8 and te == g["terminated"][2, t]
+        assert bits_off(obs, g["final_obs"][2, t]) == 0, t
+        assert abs(r - g["reward"][2, t]) <= F64_REW_TOL and te == g["terminated"][2, t] and tr == g["truncated"][2, t]
         if te or tr:
             break
     env.close()
