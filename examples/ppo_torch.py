@@ -29,6 +29,12 @@ this image, so this is a compact PPO with the same hyper-parameters where they c
   frame per step and env instead of the 715-float stack (``DeviceRollout(n_stack=5)``) and the update
   reads each minibatch through ``DeviceRollout.gather``, one launch that rebuilds the stacked rows and
   fetches the five other fields.  The minibatches hold the same bits as without the flag.
+* ``--sde-kernel`` (with ``--fused`` and gSDE; ``train(fused=True, sde_kernel=True)``): the rollout's gSDE
+  head is ``gym_usv_amd.DeviceSDE``, one HIP launch per step that rebuilds each env's exploration matrix
+  from a counter-based generator instead of storing it: no ``sample_weights`` tensor, no ``bmm``, no
+  ``Normal.log_prob``.  ``reset_noise`` is then a host integer.  The update is unchanged: it only ever
+  needed the variance.  The noise differs from torch's generator, so runs with and without the flag are
+  two samples of the same algorithm, not the same numbers.
 
 Rollout size at 4096 envs.  config_ppo's ``n_steps=2048, batch_size=64`` are for the reference's 4
 envs: 8 192 samples per update in 128 minibatches.  With 4096 envs the same n_steps would put 8.4 M
@@ -108,7 +114,7 @@ class ActorCritic(nn.Module):
 class PPO:
     """Rollout + update over a ``UsvVectorEnv`` (any registered id with a Box action space)."""
 
-    def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, frames=False, **cfg):
+    def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, frames=False, sde_kernel=False, **cfg):
         from gym_usv_amd.sb3 import DeviceFrameStack
         self.cfg = dict(CONFIG_PPO, **cfg)
         self.env, self.n_steps, self.batch_size = env, n_steps, batch_size
@@ -119,6 +125,9 @@ class PPO:
         if frames and not fused:
             raise ValueError("frames=True needs fused=True")
         self.frames = frames
+        if sde_kernel and not (fused and self.cfg["use_sde"]):
+            raise ValueError("sde_kernel=True needs fused=True and use_sde=True")
+        self.head = None
         if not fused:
             self.stack = DeviceFrameStack(self.N, D, self.cfg["n_stack"], self.device)
         torch.manual_seed(seed)
@@ -140,6 +149,11 @@ class PPO:
             self.ro = DeviceRollout(self.N, n_steps, k * D, A, self.device, env.reward.dtype,
                                     n_stack=k if frames else None)
             self.wr.reset(obs)
+            if sde_kernel:
+                from gym_usv_amd import DeviceSDE
+                # a key of its own: the env's resets draw from the same generator keyed by `seed`
+                self.head = DeviceSDE(self.N, self.cfg["hidden"][-1], A, self.device, seed ^ 0x5DE5DE5DE5DE5DE5, lo, hi,
+                                      env_id_offset=int(env.cfg.env_id_offset))
             # the update reads the rollout's own buffers
             self.b_obs, self.b_act, self.b_logp, self.b_val = self.ro.obs, self.ro.act, self.ro.logp, self.ro.val
             self._totals = (0.0, 0, 0)
@@ -159,9 +173,18 @@ class PPO:
         sde, freq = self.cfg["use_sde"], self.cfg["sde_sample_freq"]
         wr, ro = self.wr, self.ro
         for t in range(self.n_steps):
-            if sde and (t == 0 or (freq > 0 and t % freq == 0)):   # reset_noise (SB3 collect_rollouts)
-                self.W = self.model.sample_weights(self.N)
+            new_noise = sde and (t == 0 or (freq > 0 and t % freq == 0))   # reset_noise (SB3 collect_rollouts)
             obs = wr.stacked                                        # the ring's window, no clone
+            if self.head is not None:
+                if new_noise:
+                    self.head.reset_noise()
+                lat = self.model.pi_body(obs)
+                a, a_env, logp = self.head.sample(self.model.mu(lat), lat, self.model.log_std.exp())
+                ro.put_obs(t, obs, a, self.model.value(obs), logp)
+                self._step_fused(t, a_env)
+                continue
+            if new_noise:
+                self.W = self.model.sample_weights(self.N)
             dist, lat = self.model.dist(obs, validate=False)
             if sde:
                 a = dist.mean + torch.bmm(lat.unsqueeze(1), self.W).squeeze(1)
@@ -169,11 +192,15 @@ class PPO:
                 a = dist.sample()
             ro.put_obs(t, obs, a.contiguous(), self.model.value(obs), dist.log_prob(a).sum(-1))
             a_env = torch.max(torch.min(a, self.a_hi), self.a_lo)          # SB3 clips Box actions
-            o, rew, term, trunc, info = self.env.step(a_env)
-            self.abs_ye.append(o[:, 5].abs().mean() * 10.0)   # obs[5] = ye / 10 (simple_env.py:79-80)
-            _, final_stack, _ = wr.step(o, rew, info["_final_obs"], info["final_obs"])
-            ro.put_step(t, rew, term, trunc, final_stack)
-            self.env_steps += self.N
+            self._step_fused(t, a_env)
+
+    def _step_fused(self, t, a_env):
+        """The env step behind the fused wrappers and the rollout's row t of rewards and dones."""
+        o, rew, term, trunc, info = self.env.step(a_env)
+        self.abs_ye.append(o[:, 5].abs().mean() * 10.0)   # obs[5] = ye / 10 (simple_env.py:79-80)
+        _, final_stack, _ = self.wr.step(o, rew, info["_final_obs"], info["final_obs"])
+        self.ro.put_step(t, rew, term, trunc, final_stack)
+        self.env_steps += self.N
 
     @torch.no_grad()
     def rollout(self):
@@ -313,10 +340,11 @@ class PPO:
 
 
 def train(env_id="usv-simple", envs=4096, updates=10, n_steps=32, batch_size=4096, seed=0, log=print, fused=False,
-          frames=False, **cfg):
+          frames=False, sde_kernel=False, **cfg):
     import gym_usv_amd
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False)   # each step is consumed at once
-    ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, frames=frames, **cfg)
+    ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, frames=frames,
+              sde_kernel=sde_kernel, **cfg)
     hist = []
     t0 = time.perf_counter()
     for u in range(updates):
@@ -342,10 +370,14 @@ def main():
     ap.add_argument("--fused", action="store_true", help="DeviceWrappers + DeviceRollout: a sync-free rollout")
     ap.add_argument("--frames", action="store_true",
                     help="with --fused: one frame per step in the rollout, minibatches by DeviceRollout.gather")
+    ap.add_argument("--sde-kernel", action="store_true",
+                    help="with --fused and gSDE: the rollout's action head is one DeviceSDE launch per step")
     ap.add_argument("--log", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     if a.frames and not a.fused:
         ap.error("--frames needs --fused")
+    if a.sde_kernel and (not a.fused or a.no_sde):
+        ap.error("--sde-kernel needs --fused and gSDE (no --no-sde)")
     f = open(a.log, "a") if a.log else None
 
     def log(s):
@@ -356,9 +388,9 @@ def main():
     if f:
         log(json.dumps({"config": {**CONFIG_PPO, "use_sde": not a.no_sde, "env_id": a.env_id, "envs": a.envs,
                                    "n_steps": a.n_steps, "batch_size": a.batch_size, "seed": a.seed,
-                                   "fused": a.fused, "frames": a.frames}}))
+                                   "fused": a.fused, "frames": a.frames, "sde_kernel": a.sde_kernel}}))
     train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, fused=a.fused, frames=a.frames,
-          use_sde=not a.no_sde)
+          sde_kernel=a.sde_kernel, use_sde=not a.no_sde)
 
 
 if __name__ == "__main__":

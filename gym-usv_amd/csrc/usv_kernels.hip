@@ -23,6 +23,8 @@
 //   usv_rollout.hpp       RolloutBuffer + truncation bootstrap + GAE (usv_rollout_put_obs / _put_step / _gae)
 //   usv_rollout_frames_math.hpp  frame-deduplicated obs storage: rows, live mask, clear rule (host C++, no HIP)
 //   usv_rollout_frames.hpp  frame store and minibatch gather (usv_rollout_put_obs_frames / usv_rollout_gather)
+//   usv_sde_math.hpp      gSDE head: Philox numbering, Box-Muller, sums, clip, log-probability (host C++, no HIP)
+//   usv_sde.hpp           fused gSDE action head (usv_sde_sample / usv_sde_weights)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -50,6 +52,7 @@
 #include "usv_norm.hpp"
 #include "usv_rollout.hpp"
 #include "usv_rollout_frames.hpp"
+#include "usv_sde.hpp"
 
 // ============================================================================= host side
 using namespace usv;
@@ -1216,6 +1219,73 @@ int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, cons
   const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
   hipLaunchKernelGGL(rollout_gather_kernel, grid, block, 0, (hipStream_t)stream, a, f, idx, (int)B, obs_out, act_out,
                      val_out, logp_out, adv_out, ret_out);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- fused gSDE action head (usv_sde.hpp)
+// The checks of a usv_sde that need no HIP call; fills the kernels' arguments.
+static int sde_check(const usv_sde* s, SdeArgs& a) {
+  if (!s) return fail(USV_ERR_ARG, "null usv_sde");
+  if (s->n <= 0) return fail(USV_ERR_ARG, "usv_sde: n must be > 0");
+  if (s->act_dim != 1 && s->act_dim != 2) return fail(USV_ERR_ARG, "usv_sde: act_dim must be 1 or 2");
+  if (!sde_latent_ok(s->latent_dim))
+    return fail(USV_ERR_ARG, "usv_sde: latent_dim must be a multiple of 4 in [4, 4096]");
+  if (s->reserved != 0) return fail(USV_ERR_ARG, "usv_sde: reserved must be 0");
+  for (int k = 0; k < s->act_dim; ++k)
+    if (!(s->low[k] <= s->high[k])) return fail(USV_ERR_ARG, "usv_sde: low must be <= high (and neither NaN)");
+  a = SdeArgs{s->n, s->latent_dim, 0u, s->seed, s->gid0, {s->low[0], s->low[1]}, {s->high[0], s->high[1]}};
+  return USV_OK;
+}
+
+static int sde_bufs(const Buf* b, size_t nb, int& dev) {
+  switch (check_bufs(b, nb)) {
+    case kBufNull: return fail(USV_ERR_ARG, "usv_sde: null buffer");
+    case kBufAlign: return fail(USV_ERR_ARG, "usv_sde: lat is not 16-B aligned or a buffer is not 4-B aligned");
+    default: break;
+  }
+  if (check_bufs(b, nb, &dev) == kBufDevice)
+    return fail(USV_ERR_ARG, dev < 0 ? "usv_sde: the first buffer is not a device pointer"
+                                     : "usv_sde: a buffer is not a device pointer on the device that holds the first");
+  return USV_OK;
+}
+
+int usv_sde_sample(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
+                   const float* std, float* act, float* act_env, float* logp, void* stream) {
+  SdeArgs a;
+  int dev;
+  if (int rc = sde_check(s, a)) return rc;
+  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
+    return fail(USV_ERR_ARG, "usv_sde_sample: the row stride must be a multiple of 4 and >= latent_dim");
+  const Buf all[] = {{lat, 16}, {mean, 4}, {std, 4}, {act, 4}, {act_env, 4}, {logp, 4}};
+  if (int rc = sde_bufs(all, 6, dev)) return rc;
+  a.epoch = epoch;
+  DeviceGuard g(dev);
+  const dim3 grid((unsigned)(((int64_t)a.n + kWaves - 1) / kWaves)), block(kBlock);
+  if (s->act_dim == 1)
+    hipLaunchKernelGGL(sde_sample_kernel<1>, grid, block, 0, (hipStream_t)stream, a, mean, lat, stride, std, act, act_env, logp);
+  else
+    hipLaunchKernelGGL(sde_sample_kernel<2>, grid, block, 0, (hipStream_t)stream, a, mean, lat, stride, std, act, act_env, logp);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std, float* w, void* stream) {
+  SdeArgs a;
+  int dev;
+  if (int rc = sde_check(s, a)) return rc;
+  const int64_t threads = (int64_t)a.n * (a.L * s->act_dim / 4);
+  if ((threads + kBlock - 1) / kBlock > 2147483647)
+    return fail(USV_ERR_ARG, "usv_sde_weights: n * latent_dim * act_dim / 4 is above 2^31 - 1 blocks of 256");
+  const Buf all[] = {{w, 4}, {std, 4}};
+  if (int rc = sde_bufs(all, 2, dev)) return rc;
+  a.epoch = epoch;
+  DeviceGuard g(dev);
+  const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), block(kBlock);
+  if (s->act_dim == 1)
+    hipLaunchKernelGGL(sde_weights_kernel<1>, grid, block, 0, (hipStream_t)stream, a, std, w);
+  else
+    hipLaunchKernelGGL(sde_weights_kernel<2>, grid, block, 0, (hipStream_t)stream, a, std, w);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

@@ -102,9 +102,16 @@ class UsvRolloutFrames(ctypes.Structure):
                 ("frames", ctypes.c_void_p), ("bad_count", ctypes.c_void_p)]
 
 
+class UsvSde(ctypes.Structure):
+    """usv_sde: shape, generator key and Box bounds of the fused gSDE head (usv_sde_sample / usv_sde_weights)."""
+    _fields_ = [("n", ctypes.c_int32), ("latent_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("gid0", ctypes.c_uint64),
+                ("low", ctypes.c_float * 4), ("high", ctypes.c_float * 4)]
+
+
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
-_i64 = ctypes.c_int64
+_i64, _u32 = ctypes.c_int64, ctypes.c_uint32
 SIGNATURES = [
     ("usv_abi_version", ctypes.c_int, []),
     ("usv_last_error", ctypes.c_char_p, []),
@@ -150,6 +157,8 @@ SIGNATURES = [
                                                   _vp, _sz, _vp, _vp, _vp, _vp]),
     ("usv_rollout_gather", ctypes.c_int, [ctypes.POINTER(UsvRollout), ctypes.POINTER(UsvRolloutFrames), _vp, _i32, _vp,
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_sde_sample", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_sde_weights", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _vp]),
 ]
 
 _LIBS = {}
@@ -209,6 +218,19 @@ def cuda_device(device, who):
     if device.type != "cuda":
         raise UsvLibError(f"{who} runs on a ROCm GPU only (no CPU fallback)")
     return device
+
+
+def check_rows(name, t, dtype, shape, device, stride_multiple=1, align=1):
+    """A 2-D tensor read row by row in place: inner stride 1, a row stride >= the row length that is a
+    multiple of ``stride_multiple`` elements, and a base aligned to ``align`` bytes.  Returns the row stride
+    in elements; a single row has no stride of its own and reports its length."""
+    n, w = shape
+    stride = t.stride(0) if t.dim() == 2 and n > 1 else w
+    if (t.dim() != 2 or t.dtype != dtype or tuple(t.shape) != shape or t.device != device or t.stride(1) != 1 or
+            stride < w or stride % stride_multiple != 0 or t.data_ptr() % align != 0):
+        raise ValueError(f"{name} must be a {dtype} tensor of shape {shape} on {device} with inner stride 1, a row "
+                         f"stride >= {w} that is a multiple of {stride_multiple}, and a {align}-B aligned base")
+    return stride
 
 
 def check_tensor(name, t, dtype, shape, device):

@@ -508,6 +508,49 @@ int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, cons
                        float* obs_out, float* act_out, float* val_out, float* logp_out, float* adv_out,
                        float* ret_out, void* stream);
 
+/* Fused gSDE action head: SB3's StateDependentNoiseDistribution (common/distributions.py; full_std, no
+ * expln, latent not learned through the noise) at rollout time, with the per-env exploration matrix rebuilt
+ * from a counter-based generator in the launch that uses it instead of being stored.  Handle-free and
+ * stream-ordered like usv_wrap_* and usv_rollout_*; additive (ABI v5 addition).  No host sync.
+ *
+ * The matrix (replaces sample_weights: exploration_mat = Normal(0, std).rsample((n,))).  Element (j, k) of
+ * env e's [latent_dim][act_dim] matrix, flat index i = j * act_dim + k, is std[j][k] * z where z is normal
+ * number i % 4 of Philox4x32-10 block i / 4 with key (seed lo, seed hi) and counter (gid lo, gid hi, epoch,
+ * block), gid = gid0 + e.  A block's words (o0, o1, o2, o3) give z0 = r cos(2 pi u2), z1 = r sin(2 pi u2)
+ * with u1 = ((o0 >> 8) + 1) * 2^-24, u2 = (o1 >> 8) * 2^-24, r = sqrt(-2 ln u1), and z2, z3 from (o2, o3)
+ * the same way.  A new epoch is a new matrix (reset_noise: the caller increments it); the matrix does not
+ * depend on n or on how envs are sharded (gid0 = the shard's first global env id).  Use a seed other than
+ * the env's: the resets draw from the same generator keyed by usv_config.seed, counter (gid, episode, draw).
+ *
+ * usv_sde_sample(s, epoch, mean [n][A], lat [n] rows of latent_dim floats, row stride in floats, std
+ * [latent_dim][A] = exp(log_std), act [n][A], act_env [n][A], logp [n]), all float32, one launch:
+ *   noise_k = sum_j lat_j * (std_jk * z_jk)               <- get_noise: bmm(latent_sde, exploration_matrices)
+ *   act_k   = mean_k + noise_k                            <- sample: mean + noise (unclipped: the buffer's)
+ *   act_env_k = max(min(act_k, high_k), low_k)            <- the trainer's np.clip to the Box
+ *   var_k   = sum_j (lat_j lat_j) (std_jk std_jk);  s2_k = var_k + 1e-6
+ *                                                         <- proba_distribution: mm(latent_sde ** 2, std ** 2)
+ *   logp    = sum_k (-(act_k - mean_k)^2 / (2 s2_k) - 0.5 ln s2_k - 0.5 ln 2 pi)
+ *                                                         <- log_prob: Normal(mean, sqrt(s2)).log_prob(a).sum(-1)
+ * in the operation and summation order of csrc/usv_sde_math.hpp.  The matrix is never written to memory.
+ * usv_sde_weights(s, epoch, std, w [n][latent_dim][A]) writes the matrix itself (exploration_mat), from the
+ * same device functions: for inspection, tests and checkpoints.
+ *
+ * USV_ERR_ARG, before any HIP call, for a NULL usv_sde, n <= 0, act_dim not 1 or 2, latent_dim outside
+ * [4, 4096] or not a multiple of 4, reserved != 0, low[k] > high[k] or a NaN bound (k < act_dim), a row
+ * stride below latent_dim or not a multiple of 4, a NULL buffer, a lat_dev that is not 16-B aligned or
+ * another buffer that is not 4-B aligned, and a usv_sde_weights of more than 2^31 - 1 blocks of 256
+ * four-element groups.  Then for a buffer that is not device memory of the device that holds lat_dev
+ * (usv_sde_weights: w_dev). */
+typedef struct usv_sde {
+  int32_t n, latent_dim, act_dim, reserved;   /* reserved = 0 */
+  uint64_t seed, gid0;
+  float low[4], high[4];                      /* Box bounds, first act_dim used */
+} usv_sde;
+int usv_sde_sample(const usv_sde* s, uint32_t epoch, const float* mean_dev, const float* lat_dev,
+                   size_t lat_row_stride_floats, const float* std_dev, float* act_dev, float* act_env_dev,
+                   float* logp_dev, void* stream);
+int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std_dev, float* w_dev, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
