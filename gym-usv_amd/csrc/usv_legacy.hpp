@@ -17,6 +17,7 @@ constexpr double kV0MinSpeed = 0.3, kV0KAk = 5.72, kV0KYe = 0.5, kV0SigmaYe = 1.
 constexpr double kV0CAction = 1.0 / (((kPi / 2) / 2 - (-kPi / 2) / 2) / H * (((kPi / 2) / 2 - (-kPi / 2) / 2) / H));
 constexpr double kV0WAction = 0.2, kV0TMin = -30.0, kV0TMax = 36.5;
 constexpr int kFamV0 = 0, kFamYeInt = 1, kFamPid = 2;   // usv-asmc-v0, usv-asmc-ye-int-v0, usv-pid-v0
+constexpr double kYvK = 1.1 + 0.0045 * (1.01 / 0.09) - 0.1 * (0.27 / 0.09) + 0.016 * ((0.27 / 0.09) * (0.27 / 0.09));
 
 template <typename R> __device__ __forceinline__ R q32(R x) { return R((float)x); }
 
@@ -113,6 +114,49 @@ __device__ void v0_reset_draws(const State<R>& S, int e, float* row, int ep, G&&
   v0_obs<R>(row, R(0), R(0), R(0), R(ye), R(psi_ak), R(0));                      // :289-298
 }
 
+// The plant's f, C = CRB + CA and D = Dl - Dn (:132-145, :193-212) in the arithmetic the reference's state has: T =
+// float on stored float32 state, T = R on the float64 reset state (the first step).  C and D are float32 arrays
+// either way: each entry is computed in T and rounded, then the two arrays are added / subtracted in float32.
+struct V0Mats { float c02, c12, c20, c21, d00, d11, d12, d21, d22; };
+
+template <typename R, typename T>
+__device__ __forceinline__ void v0_plant(T u, T v, T r, R xu, R xuu, R& fu, R& fpsi, V0Mats& m) {
+  const T au = m_abs(u), av = m_abs(v), ar = m_abs(r);
+  const T mag = m_sqrt(u * u + v * v);
+  // :132-133 the factor holds np.power(0.27 / 0.09, 2), a float64 scalar: the last product is float64
+  const R yv = R(T(0.5) * (T(-40 * 1000) * av)) * R(kYvK);
+  const T yr = ((T(6 * (-3.141592 * 1000)) * mag) * T(0.09)) * T(0.09) * T(1.01);               // :134
+  const T nv = ((T(0.06 * (-3.141592 * 1000)) * mag) * T(0.09)) * T(0.09) * T(1.01);            // :136
+  const T nr = ((T(0.02 * (-3.141592 * 1000)) * mag) * T(0.09)) * T(0.09) * T(1.01) * T(1.01);  // :138
+  fu = R((T(MASS - Y_V_DOT) * v * r + (T(xuu) * au + T(xu) * u)) / T(MASS - X_U_DOT));           // :144
+  fpsi = R((T(-X_U_DOT + Y_V_DOT) * u * v + (nr * r)) / T(IZ - N_R_DOT));                        // :145
+  const T k = T((Y_R_DOT + N_V_DOT) / 2);
+  m.c02 = (float)(T(0) - T(MASS) * v) + (float)(T(2) * (T(Y_V_DOT) * v + k * r));
+  m.c12 = (float)(T(MASS) * u) + (float)(T(0) - T(X_U_DOT * MASS) * u);
+  m.c20 = (float)(T(MASS) * v) + (float)(T(2) * ((T(0 - Y_V_DOT) * v) - k * r));
+  m.c21 = (float)(T(0) - T(MASS) * u) + (float)(T(X_U_DOT * MASS) * u);
+  m.d00 = (float)(0 - xu) - (float)(T(xuu) * au);                                                // :207
+  m.d11 = (float)(R(0) - yv) - (float)(T(YVV) * av + T(YVR) * ar);
+  m.d12 = (float)(T(0) - yr) - (float)(T(YRV) * av + T(YRR) * ar);
+  m.d21 = (float)(T(0) - nv) - (float)(T(NVV) * av + T(NVR) * ar);
+  m.d22 = (float)(T(0) - nr) - (float)(T(NRV) * av + T(NRR) * ar);
+}
+
+// T - C nu - D nu (:214-215).  float32 nu: a float32 matmul, whose last row OpenBLAS's sgemv fused when the fixtures
+// were written, fma(a22, x2, fma(a20, x0, a21 * x1)), rows 0 and 1 summed product by product; the fixture
+// (tests/golden/legacy_scenes.npz) is the authority for that pattern.  float64 nu (first step): C and D are promoted
+// and nothing is fused.
+__device__ __forceinline__ void v0_rhs(const V0Mats& m, float t0, float t2, float u, float v, float r, float (&rhs)[3]) {
+  rhs[0] = (t0 - m.c02 * r) - m.d00 * u;
+  rhs[1] = (0.0f - m.c12 * r) - (m.d11 * v + m.d12 * r);
+  rhs[2] = (t2 - __builtin_fmaf(m.c20, u, m.c21 * v)) - __builtin_fmaf(m.d22, r, m.d21 * v);
+}
+__device__ __forceinline__ void v0_rhs(const V0Mats& m, float t0, float t2, double u, double v, double r, double (&rhs)[3]) {
+  rhs[0] = ((double)t0 - (double)m.c02 * r) - (double)m.d00 * u;
+  rhs[1] = (0.0 - (double)m.c12 * r) - ((double)m.d11 * v + (double)m.d12 * r);
+  rhs[2] = ((double)t2 - ((double)m.c20 * u + (double)m.c21 * v)) - ((double)m.d21 * v + (double)m.d22 * r);
+}
+
 template <typename R>
 __global__ __launch_bounds__(kBlock) void v0_step_kernel(State<R> S, IO<R> io) {
   const int e = blockIdx.x * kBlock + threadIdx.x;
@@ -132,18 +176,15 @@ __global__ __launch_bounds__(kBlock) void v0_step_kernel(State<R> S, IO<R> io) {
   // action_dot (:120): float32 arithmetic once the stored state is float32
   const R action_dot = first ? (a - a_last) / R(H) : R((af - (float)a_last) / (float)H);
   const R psi_d = wrap_once(a + ak);                                             // :123-124
-  const bool fast = m_abs(u) > R(1.2);                                           // :126-130
+  const float uf = (float)u, vf = (float)v, rf = (float)r;                       // the stored float32 state
+  // :128 and :164-165 compare a float32 scalar with a Python float once the state is float32: NumPy makes the
+  // constant float32, so u = float32(1.2) is not fast and Ka = float32(kmin) is not above its minimum
+  const bool fast = first ? m_abs(u) > R(1.2) : fabsf(uf) > 1.2f;                // :126-130
   const R xu = fast ? R(64.55) : R(-25.0), xuu = fast ? R(-70.92) : R(0.0);
-  // hydrodynamic terms, f, C, D: float32 (state is float32; exactly 0 on the first step)
-  const float uf = (float)u, vf = (float)v, rf = (float)r;
-  const float mag = sqrtf(uf * uf + vf * vf);
-  const float yv = (0.5f * (-40000.0f * fabsf(vf))) *
-                   (float)(1.1 + 0.0045 * (1.01 / 0.09) - 0.1 * (0.27 / 0.09) + 0.016 * ((0.27 / 0.09) * (0.27 / 0.09)));  // :132
-  const float yr = (((float)(6 * (-3.141592 * 1000)) * mag) * 0.09f) * 0.09f * 1.01f;            // :134
-  const float nv = (((float)(0.06 * (-3.141592 * 1000)) * mag) * 0.09f) * 0.09f * 1.01f;         // :136
-  const float nr = (((float)(0.02 * (-3.141592 * 1000)) * mag) * 0.09f) * 0.09f * 1.01f * 1.01f; // :138
-  const float fu = ((float)(MASS - Y_V_DOT) * vf * rf + ((float)xuu * fabsf(uf) + (float)xu * uf)) / (float)(MASS - X_U_DOT);  // :144
-  const float fpsi = ((float)(-X_U_DOT + Y_V_DOT) * uf * vf + (nr * rf)) / (float)(IZ - N_R_DOT);                             // :145
+  R fu, fpsi;
+  V0Mats m;
+  if (first) v0_plant<R, R>(u, v, r, xu, xuu, fu, fpsi, m);
+  else v0_plant<R, float>(uf, vf, rf, xu, xuu, fu, fpsi, m);
   const R e_psi = wrap_once(psi_d - psi);                                        // :147-148
   const R e_psi_dot = R(0) - r;                                                  // :149
   const R u_psi = R(1) / (R(1) + m_exp(R(10) * (m_abs(e_psi) * R(2 / kPi) - R(0.5))));  // :153
@@ -152,36 +193,33 @@ __global__ __launch_bounds__(kBlock) void v0_step_kernel(State<R> S, IO<R> io) {
   e_u_int = R(H) * (e_u + e_u_last) / R(2) + e_u_int;                            // :159 (e_u_last stale)
   const R sig_u = e_u + R(LAMBDA_U) * e_u_int;                                   // :161
   const R sig_p = e_psi_dot + R(LAMBDA_PSI) * e_psi;                             // :162
-  const R kdu = ka_u > R(KMIN_U) ? R(K_U) * m_sign(m_abs(sig_u) - R(MU_U)) : R(KMIN_U);       // :164
-  const R kdp = ka_psi > R(KMIN_PSI) ? R(K_PSI) * m_sign(m_abs(sig_p) - R(MU_PSI)) : R(KMIN_PSI);
+  const bool up_u = first ? ka_u > R(KMIN_U) : (float)ka_u > (float)KMIN_U;
+  const bool up_p = first ? ka_psi > R(KMIN_PSI) : (float)ka_psi > (float)KMIN_PSI;
+  const R kdu = up_u ? R(K_U) * m_sign(m_abs(sig_u) - R(MU_U)) : R(KMIN_U);      // :164
+  const R kdp = up_p ? R(K_PSI) * m_sign(m_abs(sig_p) - R(MU_PSI)) : R(KMIN_PSI);
   ka_u = R(H) * (kdu + kdu_l) / R(2) + ka_u;                                     // :167
   ka_psi = R(H) * (kdp + kdp_l) / R(2) + ka_psi;                                 // :170
   const R ua_u = -ka_u * m_sqrt(m_abs(sig_u)) * m_sign(sig_u) - R(K2_U) * sig_u;           // :173
   const R ua_p = -ka_psi * m_sqrt(m_abs(sig_p)) * m_sign(sig_p) - R(K2_PSI) * sig_p;       // :174
-  const R tx = (R(LAMBDA_U) * e_u - R(fu) - ua_u) / R(1.0 / (MASS - X_U_DOT));  // :176
-  const R tz = (R(LAMBDA_PSI) * e_psi - R(fpsi) - ua_p) / R(1.0 / (IZ - N_R_DOT));
+  const R tx = (R(LAMBDA_U) * e_u - fu - ua_u) / R(1.0 / (MASS - X_U_DOT));     // :176
+  const R tz = (R(LAMBDA_PSI) * e_psi - fpsi - ua_p) / R(1.0 / (IZ - N_R_DOT));
   const R tport = m_clip(tx / R(2) + tz / R(B_TH), R(kV0TMin), R(kV0TMax));      // :179-185
   const R tstbd = m_clip(tx / R(2 * C_TH) - tz / R(B_TH * C_TH), R(kV0TMin), R(kV0TMax));
   const float t0 = (float)(tport + R(C_TH) * tstbd);                             // :191 float32 T
   const float t2 = (float)(R(0.5 * B_TH) * (tport - R(C_TH) * tstbd));
-  // C = CRB + CA, D = Dl - Dn as float32 (:193-212)
-  const float c02 = (0.0f - 30.0f * vf) + 2.0f * ((float)Y_V_DOT * vf + (float)((Y_R_DOT + N_V_DOT) / 2) * rf);
-  const float c12 = (30.0f * uf) + (0.0f - (float)(X_U_DOT * MASS) * uf);
-  const float c20 = (30.0f * vf) + 2.0f * (((float)(0 - Y_V_DOT) * vf) - (float)((Y_R_DOT + N_V_DOT) / 2) * rf);
-  const float c21 = (0.0f - 30.0f * uf) + ((float)(X_U_DOT * MASS) * uf);
-  const float av = fabsf(vf), ar = fabsf(rf);
-  const float d00 = (float)(0 - xu) - (float)(xuu * m_abs(u));
-  const float d11 = (0.0f - yv) - ((float)YVV * av + (float)YVR * ar);
-  const float d12 = (0.0f - yr) - ((float)YRV * av + (float)YRR * ar);
-  const float d21 = (0.0f - nv) - ((float)NVV * av + (float)NVR * ar);
-  const float d22 = (0.0f - nr) - ((float)NRV * av + (float)NRR * ar);
-  // T - C nu - D nu (:214-215), float32 (nu is float32 after the first step, 0 on it)
-  const float rhs0 = (t0 - c02 * rf) - d00 * uf;
-  const float rhs1 = (0.0f - c12 * rf) - (d11 * vf + d12 * rf);
-  const float rhs2 = (t2 - (c20 * uf + c21 * vf)) - (d21 * vf + d22 * rf);
-  const R ud = R(MI00) * R(rhs0);                                                // :214 M^-1 (f64)
-  const R vd = R(MI11) * R(rhs1) + R(MI12) * R(rhs2);
-  const R rd = R(MI21) * R(rhs1) + R(MI22) * R(rhs2);
+  R rhs0, rhs1, rhs2;
+  if (first) {
+    R q[3];
+    v0_rhs(m, t0, t2, u, v, r, q);
+    rhs0 = q[0]; rhs1 = q[1]; rhs2 = q[2];
+  } else {
+    float q[3];
+    v0_rhs(m, t0, t2, uf, vf, rf, q);
+    rhs0 = R(q[0]); rhs1 = R(q[1]); rhs2 = R(q[2]);
+  }
+  const R ud = R(MI00) * rhs0;                                                   // :214 M^-1 (f64)
+  const R vd = R(MI11) * rhs1 + R(MI12) * rhs2;
+  const R rd = R(MI21) * rhs1 + R(MI22) * rhs2;
   u = R(H) * (ud + ud_l) / R(2) + u;                                             // :216-217
   v = R(H) * (vd + vd_l) / R(2) + v;
   r = R(H) * (rd + rd_l) / R(2) + r;
@@ -199,8 +237,8 @@ __global__ __launch_bounds__(kBlock) void v0_step_kernel(State<R> S, IO<R> io) {
   const R ye_abs = m_abs(ye);
   // compute_reward (:364-374)
   const R pa = m_abs(psi_ak);
-  const R cad = first ? R(-kV0CAction) * (action_dot * action_dot)
-                      : R((float)(-kV0CAction) * ((float)action_dot * (float)action_dot));
+  // c_action is a float64 scalar (np.power, :77): only the square is float32 on float32 state
+  const R cad = R(-kV0CAction) * (first ? action_dot * action_dot : R((float)action_dot * (float)action_dot));
   const R r_act = R(kV0WAction) * tanh(cad);
   const R r_ye = ye_abs > R(kV0SigmaYe) ? m_exp(R(-kV0KYe) * ye_abs) : m_exp(R(-kV0KYe) * (ye_abs * ye_abs) / R(kV0SigmaYe));
   const R r_ak = -m_exp(R(kV0KAk) * (pa - R(kPi)));
@@ -245,7 +283,6 @@ __global__ __launch_bounds__(kBlock) void v0_reset_kernel(State<R> S, IO<R> io) 
 // earlier (its control law: :148-155).
 constexpr double kYeIntKI = 0.001;                                               // ye_int :51
 constexpr double kPidKpU = 1.1, kPidKiU = 0.2, kPidKdU = 0.1, kPidKpPsi = 0.8, kPidKdPsi = 3.0;  // pid :40-44
-constexpr double kYvK = 1.1 + 0.0045 * (1.01 / 0.09) - 0.1 * (0.27 / 0.09) + 0.016 * ((0.27 / 0.09) * (0.27 / 0.09));
 
 template <typename R, int FAM>
 __global__ __launch_bounds__(kBlock) void legacy_step_kernel(State<R> S, IO<R> io) {

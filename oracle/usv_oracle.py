@@ -505,6 +505,24 @@ V0_T_MIN, V0_T_MAX = -30.0, 36.5                                                
 f32 = np.float32
 
 
+def _arm(env, name, cond):
+    """The named comparison, turned the other way where ``env.flip[name]`` says so (tests/legacy_scenes.py
+    forces one branch at a time to show that its scenes tell the two arms apart)."""
+    f = env.flip.get(name)
+    return cond if f is None else cond ^ np.asarray(f, dtype=bool)
+
+
+def _sign_arm(env, name, x):
+    """np.sign(x), negated where ``env.flip[name]`` says so."""
+    return np.where(_arm(env, name, np.zeros(env.n, bool)), -np.sign(x), np.sign(x))
+
+
+def _clip_arms(env, name, t):
+    """np.where(t > 36.5, 36.5, t) then np.where(t < -30, -30, t), both compares through _arm."""
+    t = np.where(_arm(env, name + "_hi", t > V0_T_MAX), V0_T_MAX, t)
+    return np.where(_arm(env, name + "_lo", t < V0_T_MIN), V0_T_MIN, t)
+
+
 class AsmcV0Batch:
     """Batched restatement of the legacy ``UsvAsmcEnv`` (id usv-asmc-v0, usv_asmc_env.py:14-401).
 
@@ -530,6 +548,7 @@ class AsmcV0Batch:
         self.state = z(6)
         self.first = np.ones(n, bool)   # reference state is float64 until the first step
         self.rngs = [None] * n
+        self.flip, self.q = {}, {}      # forced comparisons; the last step's deciding quantities
 
     def reset_env(self, i, seed=None):
         if seed is not None or self.rngs[i] is None:
@@ -573,8 +592,15 @@ class AsmcV0Batch:
         ad64 = (a.astype(np.float64) - a_last) / H
         ad32 = ((a - a_last.astype(np.float32)) / np.float32(H)).astype(np.float64)
         action_dot = np.where(fs, ad32, ad64)
-        psi_d = wrap_once(a.astype(np.float64) + ak)                      # :123-124
-        fast = np.abs(u) > 1.2                                             # :126-130
+        psi_d_raw = a.astype(np.float64) + ak
+        psi_d = wrap_once(psi_d_raw)                                       # :123-124
+        # :128 abs(upsilon[0]) > 1.2 and :164-165 Ka > kmin compare a float32 scalar with a Python float once
+        # the stored state is float32: NumPy 2 makes the constant float32, so u = float32(1.2) is not fast
+        # and Ka = float32(kmin) is not above it; the float64 reset state compares in float64
+        def thr(c):
+            return np.where(fs, np.float64(np.float32(c)), c)
+        q_drag = np.abs(u) - thr(1.2)
+        fast = _arm(self, "drag", q_drag > 0)                              # :126-130
 
         def f32ops(vals):
             """Evaluate in float32 where the env's state is float32 (NumPy 2 promotion)."""
@@ -590,6 +616,10 @@ class AsmcV0Batch:
             return yv, yr, nv, nr
         y64, y32 = hydro(np.float64), hydro(np.float32)
         yv, yr, nv, nr = (np.where(fs, b.astype(np.float64), c) for b, c in zip(y32, y64))   # :132-139
+        # :133 np.power(0.27 / 0.09, 2) is a float64 scalar, not a Python float, so Yv's last product is taken in
+        # float64 even on float32 state (and rounded once, into Dl)
+        yv = np.where(fs, (np.float32(0.5) * (np.float32(-40 * 1000) * np.abs(v.astype(np.float32)))).astype(np.float64)
+                      * (1.1 + 0.0045 * (1.01 / 0.09) - 0.1 * (0.27 / 0.09) + 0.016 * np.power((0.27 / 0.09), 2)), yv)
         xu = np.where(fast, 64.55, -25.0)
         xuu = np.where(fast, -70.92, 0.0)
 
@@ -602,7 +632,8 @@ class AsmcV0Batch:
         fu64, fp64 = fpart(np.float64)
         f_u = np.where(fs, fu32.astype(np.float64), fu64)                  # :144
         f_psi = np.where(fs, fp32.astype(np.float64), fp64)                # :145
-        e_psi = wrap_once(psi_d - psi)                                     # :147-148
+        e_psi_raw = psi_d - psi
+        e_psi = wrap_once(e_psi_raw)                                       # :147-148
         e_psi_dot = 0 - r                                                  # :149
         u_psi = 1 / (1 + np.exp(10 * (np.abs(e_psi) * (2 / np.pi) - 0.5)))    # :153
         u_d = (ds - V0_MIN_SPEED) * u_psi + V0_MIN_SPEED                   # :155-156
@@ -610,16 +641,20 @@ class AsmcV0Batch:
         e_u_int = H * (e_u + e_u_last) / 2 + e_u_int                       # :159 (e_u_last stale)
         sig_u = e_u + LAMBDA_U * e_u_int                                   # :161
         sig_p = e_psi_dot + LAMBDA_PSI * e_psi                             # :162
-        kdu = np.where(ka_u > KMIN_U, K_U * np.sign(np.abs(sig_u) - MU_U), KMIN_U)       # :164
-        kdp = np.where(ka_psi > KMIN_PSI, K_PSI * np.sign(np.abs(sig_p) - MU_PSI), KMIN_PSI)
+        q_ka_u, q_ka_psi = ka_u - thr(KMIN_U), ka_psi - thr(KMIN_PSI)
+        q_sig_u, q_sig_psi = np.abs(sig_u) - MU_U, np.abs(sig_p) - MU_PSI
+        su, sp = _sign_arm(self, "sig_u", q_sig_u), _sign_arm(self, "sig_psi", q_sig_psi)
+        kdu = np.where(_arm(self, "ka_u", q_ka_u > 0), K_U * su, KMIN_U)                 # :164
+        kdp = np.where(_arm(self, "ka_psi", q_ka_psi > 0), K_PSI * sp, KMIN_PSI)
         ka_u = H * (kdu + kdu_l) / 2 + ka_u                                # :167
         ka_psi = H * (kdp + kdp_l) / 2 + ka_psi                            # :170
         ua_u = -ka_u * np.sqrt(np.abs(sig_u)) * np.sign(sig_u) - K2_U * sig_u            # :173
         ua_p = -ka_psi * np.sqrt(np.abs(sig_p)) * np.sign(sig_p) - K2_PSI * sig_p        # :174
         tx = (LAMBDA_U * e_u - f_u - ua_u) / (1 / (MASS - X_U_DOT))       # :176
         tz = (LAMBDA_PSI * e_psi - f_psi - ua_p) / (1 / (IZ - N_R_DOT))   # :177
-        tport = np.clip(tx / 2 + tz / B_TH, V0_T_MIN, V0_T_MAX)            # :179-185
-        tstbd = np.clip(tx / (2 * C_TH) - tz / (B_TH * C_TH), V0_T_MIN, V0_T_MAX)
+        tport_raw, tstbd_raw = tx / 2 + tz / B_TH, tx / (2 * C_TH) - tz / (B_TH * C_TH)
+        tport = _clip_arms(self, "tport", tport_raw)                       # :179-185
+        tstbd = _clip_arms(self, "tstbd", tstbd_raw)
         t0 = (tport + C_TH * tstbd).astype(np.float32)                     # :191 float32 T
         t2 = (0.5 * B_TH * (tport - C_TH * tstbd)).astype(np.float32)
         # CRB, CA, Dl, Dn as float32 arrays (:193-212), entries computed in the stored dtype
@@ -634,20 +669,31 @@ class AsmcV0Batch:
         c21 = cast(np.where(fs, (0 - m * uu).astype(np.float64), 0 - MASS * u)) + cast(np.where(fs, (np.float32(X_U_DOT * MASS) * uu).astype(np.float64), X_U_DOT * MASS * u))
         av = np.where(fs, np.abs(vv).astype(np.float64), np.abs(v))
         ar = np.where(fs, np.abs(rr).astype(np.float64), np.abs(r))
-        d00 = cast(0 - xu) - cast(xuu * np.abs(u))
+        d00 = cast(0 - xu) - cast(np.where(fs, (xuu.astype(np.float32) * np.abs(uu)).astype(np.float64), xuu * np.abs(u)))
         d11 = cast(0 - yv) - cast(f32ops(lambda dt: dt(YVV) * av.astype(dt) + dt(YVR) * ar.astype(dt)))
         d12 = cast(0 - yr) - cast(f32ops(lambda dt: dt(YRV) * av.astype(dt) + dt(YRR) * ar.astype(dt)))
         d21 = cast(0 - nv) - cast(f32ops(lambda dt: dt(NVV) * av.astype(dt) + dt(NVR) * ar.astype(dt)))
         d22 = cast(0 - nr) - cast(f32ops(lambda dt: dt(NRV) * av.astype(dt) + dt(NRR) * ar.astype(dt)))
         # T - C nu - D nu: float32 products/sums where nu is float32, float64 on the first step
+        # The float32 matmul of a 3x3 by a 3-vector (OpenBLAS sgemv under NumPy, as it ran when the fixtures were
+        # written) sums rows 0 and 1 product by product and fuses row 2: fma(a22, x2, fma(a20, x0, a21 * x1)).
+        # The float64 matmul of the first step and of the float64 ids does not fuse.  A float32 product is exact
+        # in float64, so the fused step is the float64 sum rounded once more (a double rounding: 2^-29 of cases).
+        def fma32(a, b, c):
+            return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
         def rhs(dt):
             U, V, Rr = u.astype(dt), v.astype(dt), r.astype(dt)
             cn0 = c02.astype(dt) * Rr
             cn1 = c12.astype(dt) * Rr
-            cn2 = c20.astype(dt) * U + c21.astype(dt) * V
             dn0 = d00.astype(dt) * U
             dn1 = d11.astype(dt) * V + d12.astype(dt) * Rr
-            dn2 = d21.astype(dt) * V + d22.astype(dt) * Rr
+            if dt is np.float32:
+                cn2 = fma32(c20, U, c21 * V)
+                dn2 = fma32(d22, Rr, d21 * V)
+            else:
+                cn2 = c20.astype(dt) * U + c21.astype(dt) * V
+                dn2 = d21.astype(dt) * V + d22.astype(dt) * Rr
             return ((t0.astype(dt) - cn0) - dn0, (dt(0) - cn1) - dn1, (t2.astype(dt) - cn2) - dn2)
         r32, r64 = rhs(np.float32), rhs(np.float64)
         rhs0, rhs1, rhs2 = (np.where(fs, b.astype(np.float64), c) for b, c in zip(r32, r64))
@@ -667,22 +713,28 @@ class AsmcV0Batch:
         pd = r
         x = H * (xd + xd_l) / 2 + x                                        # :225
         y = H * (yd + yd_l) / 2 + y
-        psi = H * (pd + pd_l) / 2 + psi
-        psi = wrap_once(psi)                                               # :228-229
+        psi_raw = H * (pd + pd_l) / 2 + psi
+        psi = wrap_once(psi_raw)                                           # :228-229
         psi_ak = wrap_once(psi - ak)                                       # :231-232
         ye = -(x - x0) * np.sin(ak) + (y - y0) * np.cos(ak)                # :234
         ye_abs = np.abs(ye)
         # compute_reward (:364-374)
         pa = np.abs(psi_ak)
         ad = np.where(fs, np.power(action_dot.astype(np.float32), 2).astype(np.float64), np.power(action_dot, 2))
-        cad = np.where(fs, (np.float32(-V0_C_ACTION) * ad.astype(np.float32)).astype(np.float64), -V0_C_ACTION * ad)
+        cad = -V0_C_ACTION * ad                  # c_action is a float64 scalar (np.power, :77): only the square is float32
         r_act = V0_W_ACTION * np.tanh(cad)
         r_ye = np.where(ye_abs > V0_SIGMA_YE, np.exp(-V0_K_YE * ye_abs), np.exp(-V0_K_YE * np.power(ye_abs, 2) / V0_SIGMA_YE))
         r_ak = -np.exp(V0_K_AK * (pa - np.pi))
-        reward = np.where(pa < np.pi / 2, r_act + r_ye, r_ak)
+        reward = np.where(_arm(self, "rew_ak", pa < np.pi / 2), r_act + r_ye, r_ak)
         v_ak = np.sin(psi_ak) * u + np.cos(psi_ak) * v                     # body_to_path :376-390
         done = (ye_abs > 10) | (np.abs(x) > 30)                             # :241-245
         reward = np.where(done, -1.0, reward)
+        self.q = dict(drag=q_drag, ka_u=q_ka_u, ka_psi=q_ka_psi, sig_u=q_sig_u, sig_psi=q_sig_psi, sigma_u=sig_u,
+                      sigma_psi=sig_p, tport_hi=tport_raw - V0_T_MAX, tport_lo=tport_raw - V0_T_MIN,
+                      tstbd_hi=tstbd_raw - V0_T_MAX, tstbd_lo=tstbd_raw - V0_T_MIN, wrap_d=np.abs(psi_d_raw) - np.pi,
+                      wrap_e=np.abs(e_psi_raw) - np.pi, wrap_psi=np.abs(psi_raw) - np.pi, wrap_ak=np.abs(psi - ak) - np.pi,
+                      rew_ak=pa - np.pi / 2, ye1=ye_abs - V0_SIGMA_YE, ye10=ye_abs - 10, x_hi=x - 30, x_lo=x + 30,
+                      ye=ye, adot=np.abs(action_dot), first=np.where(fs, -1.0, 1.0))
         q = lambda z: z.astype(np.float32).astype(np.float64)              # stored float32 (:247-251)
         self.state = np.stack([q(u), q(v_ak), q(r), q(ye), q(psi_ak), a.astype(np.float64)], axis=1)
         self.velocity = np.stack([q(u), q(v), q(r)], axis=1)
@@ -735,6 +787,7 @@ class LegacyF64Batch:
         self.target = z(6)          # x_0, y_0, desired_speed, ak, x_d, y_d
         self.state = z(6)
         self.rngs = [None] * n
+        self.flip, self.q = {}, {}      # forced comparisons; the last step's deciding quantities
 
     def reset_env(self, i, seed=None):
         if seed is not None or self.rngs[i] is None:
@@ -772,8 +825,10 @@ class LegacyF64Batch:
         xd_l, yd_l, pd_l, ud_l, vd_l, rd_l, e_u_last, kdu_l, kdp_l, ye_last = (self.last[:, k] for k in range(10))
         x0, y0, ds, ak = (self.target[:, k] for k in range(4))
         action_dot = (a - self.state[:, 5]) / H                            # :113
-        psi_d = wrap_once(a + ak)                                          # :116-117
-        fast = np.abs(u) > 1.2                                             # :119-123
+        psi_d_raw = a + ak
+        psi_d = wrap_once(psi_d_raw)                                       # :116-117
+        q_drag = np.abs(u) - 1.2
+        fast = _arm(self, "drag", q_drag > 0)                              # :119-123
         xu = np.where(fast, 64.55, -25.0)
         xuu = np.where(fast, -70.92, 0.0)
         mag = np.sqrt(np.power(u, 2) + np.power(v, 2))
@@ -784,17 +839,23 @@ class LegacyF64Batch:
         g_u, g_psi = 1 / (MASS - X_U_DOT), 1 / (IZ - N_R_DOT)              # :134-138
         f_u = ((MASS - Y_V_DOT) * v * r + (xuu * np.abs(u) + xu * u)) / (MASS - X_U_DOT)
         f_psi = ((-X_U_DOT + Y_V_DOT) * u * v + (nr * r)) / (IZ - N_R_DOT)
-        e_psi = wrap_once(psi_d - psi)                                     # :140-152
+        e_psi_raw = psi_d - psi
+        e_psi = wrap_once(e_psi_raw)                                       # :140-152
         e_psi_dot = 0 - r
         u_psi = 1 / (1 + np.exp(10 * (np.abs(e_psi) * (2 / np.pi) - 0.5)))
         u_d = (ds - V0_MIN_SPEED) * u_psi + V0_MIN_SPEED
         e_u = u_d - u
         e_u_int = H * (e_u + e_u_last) / 2 + e_u_int
+        q = {}
         if self.family == "ye_int":                                        # ASMC, :154-170
             sig_u = e_u + LAMBDA_U * e_u_int
             sig_p = e_psi_dot + LAMBDA_PSI * e_psi
-            kdu = np.where(ka_u > KMIN_U, K_U * np.sign(np.abs(sig_u) - MU_U), KMIN_U)
-            kdp = np.where(ka_psi > KMIN_PSI, K_PSI * np.sign(np.abs(sig_p) - MU_PSI), KMIN_PSI)
+            q_sig_u, q_sig_psi = np.abs(sig_u) - MU_U, np.abs(sig_p) - MU_PSI
+            su, sp = _sign_arm(self, "sig_u", q_sig_u), _sign_arm(self, "sig_psi", q_sig_psi)
+            kdu = np.where(_arm(self, "ka_u", ka_u > KMIN_U), K_U * su, KMIN_U)
+            kdp = np.where(_arm(self, "ka_psi", ka_psi > KMIN_PSI), K_PSI * sp, KMIN_PSI)
+            q = dict(ka_u=ka_u - KMIN_U, ka_psi=ka_psi - KMIN_PSI, sig_u=q_sig_u, sig_psi=q_sig_psi, sigma_u=sig_u,
+                     sigma_psi=sig_p)
             ka_u = H * (kdu + kdu_l) / 2 + ka_u
             ka_psi = H * (kdp + kdp_l) / 2 + ka_psi
             ua_u = (-ka_u * np.power(np.abs(sig_u), 0.5) * np.sign(sig_u)) - (K2_U * sig_u)
@@ -808,12 +869,10 @@ class LegacyF64Batch:
             ua_p = (PID_KP_PSI * e_psi) + (PID_KD_PSI * e_psi_dot)
             tx = (-f_u + ua_u) / g_u
             tz = (-f_psi + ua_p) / g_psi
-        tport = tx / 2 + tz / B_TH                                         # :172-178
-        tstbd = tx / (2 * C_TH) - tz / (B_TH * C_TH)
-        tport = np.where(tport > 36.5, 36.5, tport)
-        tport = np.where(tport < -30, -30.0, tport)
-        tstbd = np.where(tstbd > 36.5, 36.5, tstbd)
-        tstbd = np.where(tstbd < -30, -30.0, tstbd)
+        tport_raw = tx / 2 + tz / B_TH                                     # :172-178
+        tstbd_raw = tx / (2 * C_TH) - tz / (B_TH * C_TH)
+        tport = _clip_arms(self, "tport", tport_raw)
+        tstbd = _clip_arms(self, "tstbd", tstbd_raw)
         t0 = tport + C_TH * tstbd                                          # :184
         t2 = 0.5 * B_TH * (tport - C_TH * tstbd)
         # C = CRB + CA, D = Dl - Dn (:186-205); only their non-zero entries enter C nu, D nu
@@ -840,7 +899,8 @@ class LegacyF64Batch:
         xd, yd, pd = cj * u - sj * v, sj * u + cj * v, r
         x = H * (xd + xd_l) / 2 + x                                        # :217-219
         y = H * (yd + yd_l) / 2 + y
-        psi = wrap_once(H * (pd + pd_l) / 2 + psi)                         # :221-222
+        psi_raw = H * (pd + pd_l) / 2 + psi
+        psi = wrap_once(psi_raw)                                           # :221-222
         psi_ak = wrap_once(psi - ak)                                       # :224-225
         ye = -(x - x0) * np.sin(ak) + (y - y0) * np.cos(ak)               # :227
         ye_abs = np.abs(ye)
@@ -848,19 +908,26 @@ class LegacyF64Batch:
         r_act = V0_W_ACTION * np.tanh(-V0_C_ACTION * np.power(action_dot, 2))
         r_ak = -np.exp(V0_K_AK * (pa - np.pi))
         if self.family == "ye_int":
-            ye_int = np.where(np.sign(ye) != np.sign(ye_last), 0.0, ye_int)   # :230-232
+            q["ye_last"] = ye_last
+            ye_int = np.where(_arm(self, "ye_restart", np.sign(ye) != np.sign(ye_last)), 0.0, ye_int)   # :230-232
             ye_int = H * (ye + ye_last) + ye_int
             ye_last = ye
             ye_obs = ye + YE_INT_K_I * ye_int                              # ye_ss (:235)
-            reward = r_act + np.where(pa < np.pi / 2, np.exp(-V0_K_YE * ye_abs), r_ak)   # :350-360
+            reward = r_act + np.where(_arm(self, "rew_ak", pa < np.pi / 2), np.exp(-V0_K_YE * ye_abs), r_ak)   # :350-360
         else:
             ye_obs = ye
             r_ye = np.where(ye_abs > V0_SIGMA_YE, np.exp(-V0_K_YE * ye_abs),
                             np.exp(-V0_K_YE * np.power(ye_abs, 2) / V0_SIGMA_YE))
-            reward = np.where(pa < np.pi / 2, r_act + r_ye, r_ak)         # usv_pid_env.py:329-338
+            reward = np.where(_arm(self, "rew_ak", pa < np.pi / 2), r_act + r_ye, r_ak)   # usv_pid_env.py:329-338
         v_ak = np.sin(psi_ak) * u + np.cos(psi_ak) * v                     # body_to_path :239, :362-376
         done = (ye_abs > LEGACY_MAX_YE) | (x < LEGACY_MIN_X)                # :241-245
         reward = np.where(done, -1.0, reward)
+        q.update(drag=q_drag, tport_hi=tport_raw - V0_T_MAX, tport_lo=tport_raw - V0_T_MIN, tstbd_hi=tstbd_raw - V0_T_MAX,
+                 tstbd_lo=tstbd_raw - V0_T_MIN, wrap_d=np.abs(psi_d_raw) - np.pi, wrap_e=np.abs(e_psi_raw) - np.pi,
+                 wrap_psi=np.abs(psi_raw) - np.pi, wrap_ak=np.abs(psi - ak) - np.pi, rew_ak=pa - np.pi / 2,
+                 ye1=ye_abs - V0_SIGMA_YE, ye10=ye_abs - LEGACY_MAX_YE, x_min=x - LEGACY_MIN_X, ye=ye,
+                 adot=np.abs(action_dot))
+        self.q = q
         self.state = np.stack([u, v_ak, r, ye_obs, psi_ak, a], axis=1)
         self.velocity = np.stack([u, v, r], axis=1)
         self.position = np.stack([x, y, psi], axis=1)
