@@ -188,6 +188,28 @@ __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirs
 // wave64 ballot of a bool straight from its lane mask (HIP's __ballot(int) round-trips the
 // predicate through a VGPR: v_cndmask + v_cmp_ne per call)
 __device__ __forceinline__ unsigned long long ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// The two 32-lane halves of a ballot as scalars.  Pinned to SGPRs: a test of one half (any lane of
+// env A / env B) is then a scalar compare, where the compiler otherwise copies the mask to VGPRs and
+// compares 64-bit values on the VALU.
+struct BallotHalves { unsigned lo, hi; };
+__device__ __forceinline__ BallotHalves ballot_halves(unsigned long long m) {
+  BallotHalves h{(unsigned)m, (unsigned)(m >> 32)};
+  asm("" : "+s"(h.lo), "+s"(h.hi));
+  return h;
+}
+// Per lane: a in lanes 0..31, b in lanes 32..63 (a, b wave-uniform), as a lane mask made of two
+// scalar selects.
+__device__ __forceinline__ bool half_lanes(bool a, bool b) {
+  return __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)(b ? ~0u : 0u) << 32) | (a ? ~0u : 0u));
+}
+// p + a per-lane 32-bit byte offset.  With a wave-uniform p the access takes the scalar-base form
+// (SGPR pair + one VGPR offset): no 64-bit address is built per lane.  The offset passes through an
+// empty asm: the compiler otherwise splits a loop-invariant part off it, hoists that zero-extended
+// as a 64-bit VGPR pair and adds 64-bit vector addresses after all.
+template <typename T> __device__ __forceinline__ T* at_bytes(T* p, unsigned bytes) {
+  asm("" : "+v"(bytes));
+  return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + bytes);
+}
 
 template <typename R> struct Bits;
 template <> struct Bits<float> { using T = unsigned int; };

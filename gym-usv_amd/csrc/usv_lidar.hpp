@@ -418,9 +418,11 @@ __device__ __forceinline__ void lidar_window2(float dx, float dy, float key, flo
     // and the two max-scans run interleaved; pass 1's carry is pass 0's last mark (18.88 -> 18.70 us
     // per step at 65 536 envs, tools/exp_step_ab.sh)
     QCOUNT(9, 2);
+    // One masked write for both passes' marks, its destination selected on the LDS address (a write
+    // per pass is a three-way exec nest); the marks of passes >= 2 are written by the loop below.
     mark2[l] = 0;
-    if (mpass == 0) *mslot = mk0;
-    if (mpass == 1) mark2[off & (kWave - 1)] = mk0;
+    int* const mdst = (mpass == 1 ? mark2 : L.mark) + (off & (kWave - 1));
+    if ((unsigned)mpass <= 1u) *mdst = mk0;
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");   // marks and records visible
     __builtin_amdgcn_wave_barrier();
     int m0 = L.mark[l], m1 = mark2[l];
@@ -477,12 +479,13 @@ __device__ __forceinline__ void lidar_wave2(float* rows, int os, int nl, float p
   const float d = l_sqrt(m_fma(dx, dx, dy * dy));
   const float key = valid ? d - rr : big<float>();                              // simple_env.py:205-206
   // ballots of plain compares ANDed on the SALU (a ballot of an ANDed condition makes the compiler
-  // materialise it per lane first)
+  // materialise it per lane first), and their halves tested there too (ballot_halves)
   const unsigned long long vm = ballot(valid);
-  const unsigned long long tb = vm & ballot(key < (float)kTermDist);            // :334
-  A.term = (unsigned)tb != 0u; B.term = (unsigned)(tb >> 32) != 0u;
+  const BallotHalves tb = ballot_halves(vm & ballot(key < (float)kTermDist));   // :334
+  A.term = tb.lo != 0u; B.term = tb.hi != 0u;
   A.far = B.far = false;
-  const bool far = (vm & ballot(d >= (float)(0.99 * kSensorMax))) != 0;
+  const BallotHalves fb = ballot_halves(vm & ballot(d >= (float)(0.99 * kSensorMax)));
+  const bool far = (fb.lo | fb.hi) != 0u;
   lidar_window2(dx, dy, key, d, rr, valid, far, c0r, s0r, reinterpret_cast<float4*>(rows), WinLds{slot, mark, rayoff},
                 mark2, A, B, qp, rotA, rotB, wout);
 }

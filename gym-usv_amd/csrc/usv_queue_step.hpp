@@ -245,9 +245,12 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
   // Per-lane and per-block invariants of the pair loop that do not depend on phase 1, computed (and
   // pinned: the compiler otherwise sinks them to the loop's preheader) ahead of the barrier by the
   // waves that only wait there; the dynamics waves, which the barrier waits for, do it after it.
-  // hpk: the per-row layout's obs-header lanes (SPAN = false), loop-invariant, packed in one register:
-  // lanes 0..14 store env A's header value hi, 15..29 env B's, 30..63 repeat lane 29; the record slot
-  // of value hi (qrec_hdr) in bits 8..12, bit 16: env B's lane, bit 17: a constant entry (1, 10, 12-14).
+  // hpk: the per-row layout's obs-header lanes (SPAN = false), loop-invariant, packed in one register
+  // (a second one is one too many for the dynamics waves, which carry it through phase 1):
+  // lanes 0..14 store env A's header value hi, 15..29 env B's, 30..63 repeat lane 29.  Bits 0..9: the
+  // lane's byte offset from env A's obs row (value hi of its row, env B's lanes one row on); bits
+  // 10..13: the record slot of value hi (qrec_hdr), bits 14 and 16: env B's lane (so bits 10..14 index
+  // the value from env A's record, kQRec = 16 floats per record); bit 17: a constant entry (1, 10, 12-14).
   // oblk: this block's obstacle rows (pair p at 2 p rowb bytes).  ob: see pair_shift below.
   int hpk = 0;
   const float* oblk = nullptr;
@@ -257,7 +260,9 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
       const int hl = min(l, 2 * kHdr - 1);
       const int hi = hl >= kHdr ? hl - kHdr : hl;
       const int hrec = hi == 0 ? 6 : (hi <= 9 ? hi + 5 : 15);
-      hpk = hi | (hrec << 8) | ((hl >= kHdr) << 16) | ((hi == 1 || hi == 10 || hi >= 12) << 17);
+      static_assert(kQRec == 16 && 4 * (kHdr + kObsDim) < 1024, "hpk fields");
+      hpk = 4 * (hi + (hl >= kHdr ? kObsDim : 0)) | (hrec << 10) | ((hl >= kHdr) << 14) | ((hl >= kHdr) << 16) |
+            ((hi == 1 || hi == 10 || hi >= 12) << 17);
       asm volatile("" : "+v"(hpk));
     }
     oblk = S.orow(eb);
@@ -295,7 +300,9 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
   unsigned wsum = 0;                                   // (diagnostic: window sizes of this wave's pairs)
 #endif
   const bool hb = l >= 32;
-  auto pair_hasb = [&](int p) { return 2 * p + 1 < nbe; };
+  // FULL (D): every pair of the block has its env B (nbe is even), so `hasB` is the constant true and
+  // the lone-env selects fold away; the only block of a launch with an odd nbe runs the general body.
+  auto pair_hasb = [&](auto full, int p) __attribute__((always_inline)) { return decltype(full)::value || 2 * p + 1 < nbe; };
 
   // An env pair's two obs rows are one 1144-B span, stored as five 256-B wave stores from the span's
   // first 32-B sector: every sector but the two at the span's ends is written whole by one write-through
@@ -306,16 +313,19 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
   // no B): pose, meta and the obs-header value this lane stores (lanes sh..sh+14: env A's entries
   // 0..14, sh+15..sh+29: env B's; no env B: sh = 0 and lanes 15..29 repeat env A's).  Read one pair
   // ahead (after the current pair's scan), so the LDS latency overlaps the current pair's stores.
-  auto rec_of = [&](int c, float4& P, float4& M, float& H) {
+  auto rec_of = [&](auto full, int c, float4& P, float4& M, float& H) __attribute__((always_inline)) {
+    constexpr bool FULL = decltype(full)::value;
     const int c0 = 2 * c;
-    const bool cB = pair_hasb(c);
-    const int kk = (hb && cB) ? c0 + 1 : c0;
+    const bool cB = pair_hasb(full, c);
+    const int kk = FULL ? c0 + (int)((unsigned)l >> 5) : ((hb && cB) ? c0 + 1 : c0);
     const float* const rk = recs + kk * kQRec;
     P = *reinterpret_cast<const float4*>(rk);
     M = *reinterpret_cast<const float4*>(rk + 4);
     if constexpr (FUSED) M.y = __int_as_float(__float_as_int(M.y) | qnob[kk]);   // n_obs | truncated << 16
     if constexpr (!SPAN) {                             // (the constant entries are selected at the store)
-      H = recs[((((hpk >> 16) & 1) && cB) ? c0 + 1 : c0) * kQRec + ((hpk >> 8) & 31)];
+      // (FULL: bits 10..14 of hpk index env B's lanes' values one record on)
+      H = FULL ? recs[c0 * kQRec + ((hpk >> 10) & 31)]
+               : recs[((((hpk >> 16) & 1) && cB) ? c0 + 1 : c0) * kQRec + ((hpk >> 10) & 15)];
       return;
     }
     const int hl = min(max(l - ((SPAN && cB) ? pair_shift(c) : 0), 0), 2 * kHdr - 1);
@@ -328,12 +338,24 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
     asm volatile("" : "+v"(v));
     H = cst ? hc : v;
   };
+  // The pair loop with its same-step resets, in two instantiations: the block runs one of them.
+  // (One lambda around both loops rather than around the loop body alone: each copy then keeps the
+  // original's shape, one flat loop, and only its own loop invariants live across the reset path.)
+  auto run_pairs = [&](auto full) __attribute__((always_inline)) {
+  // The block's first obs row, reward and flags.  Every store of the pair loop is one of these
+  // wave-uniform bases plus a 32-bit lane offset that includes the pair's offset in the block
+  // (at_bytes).  Computed here, not with loop_setup's values: ahead of phase 1 they cost it registers,
+  // and a pointer pinned by an asm has lost its address space (its stores would be flat ones).
+  float* const bobs = io.obs + (size_t)eb * kObsDim;
+  float* const brew = io.rew + eb;
+  uint8_t* const bterm = io.term + eb;
+  [[maybe_unused]] uint8_t* const bdone = DONE ? io.done + eb : nullptr;
   for (;;) {
     unsigned done = 0;
     int de0 = 0;
     float4 pose = make_float4(0.f, 0.f, 0.f, 0.f), meta = pose;
     float hv = 0.0f;
-    if (cur >= 0) rec_of(cur, pose, meta, hv);
+    if (cur >= 0) rec_of(full, cur, pose, meta, hv);
     while (cur >= 0) {
       int nxt = (int)__builtin_amdgcn_readlane(tk, 0);
       QCOUNT(8, 1);
@@ -342,15 +364,16 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
       float* const nbuf = odd ? rowbuf0 : rowbuf1;
       const int k0 = 2 * cur;
       const int e0 = eb + k0;
-      const bool hasB = pair_hasb(cur);
+      const bool hasB = pair_hasb(full, cur);
       if (nxt >= np) nxt = -1;
       if (nxt >= 0) {                                  // wave-uniform
         if (l == 0) tk = atomicAdd(qctr, 1u);
-        dma_copy_at(oblk, 2 * rowb * nxt, nbuf, (pair_hasb(nxt) ? 2 : 1) * rowb);
+        dma_copy_at(oblk, 2 * rowb * nxt, nbuf, (pair_hasb(full, nxt) ? 2 : 1) * rowb);
       }
-      // this lane's env: lanes 0..31 env A, 32..63 env B (env A again when there is no B)
-      const int kl = (hb && hasB) ? k0 + 1 : k0;
-      const int el = e0 + (kl - k0);
+      // this lane's env in the block: lanes 0..31 env A, 32..63 env B (env A again when there is no B);
+      // the element of the reward / flag stores (kept in 32 bits: a select would be widened into a
+      // 64-bit address operand)
+      const unsigned kl = (unsigned)k0 + (((unsigned)l >> 5) & (hasB ? 1u : 0u));
       const int nt = __float_as_int(meta.y);
       // the pair's span offset and the lane rotations of the two scans that put each reading in the
       // lane that stores it (no env B: the rows are stored as in round 3, unrotated)
@@ -370,19 +393,21 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
 #endif
       float4 pose_n = pose, meta_n = meta;
       float hv_n = hv;
-      if (nxt >= 0) rec_of(nxt, pose_n, meta_n, hv_n);   // the next pair's record (wave-uniform)
+      if (nxt >= 0) rec_of(full, nxt, pose_n, meta_n, hv_n);   // the next pair's record (wave-uniform)
       // collision (:153-156): two compares and ballots per env (a fminf of the two readings would
-      // canonicalise both first)
+      // canonicalise both first); "any lane" is tested on the scalar unit (ballot_halves)
       const float kc = (float)kCollDist;
-      const bool collA = (ballot(sa.rd0 < kc) | ballot(sa.rd1 < kc)) != 0;
-      const bool collB = hasB ? (ballot(sb.rd0 < kc) | ballot(sb.rd1 < kc)) != 0 : collA;
+      const BallotHalves ca = ballot_halves(ballot(sa.rd0 < kc) | ballot(sa.rd1 < kc));
+      const BallotHalves cb = ballot_halves(ballot(sb.rd0 < kc) | ballot(sb.rd1 < kc));
+      const bool collA = (ca.lo | ca.hi) != 0u;
+      const bool collB = hasB ? (cb.lo | cb.hi) != 0u : collA;
       const bool termB = hasB ? sb.term : sa.term;
-      float* const rowA = io.obs + (size_t)e0 * kObsDim;
+      const unsigned po = (unsigned)k0 * (unsigned)(kObsDim * 4);   // env A's obs row in the block, bytes
       // the obs rows (header :91-96, sensors :82-83): five stores either way, so the loop's count of
       // memory instructions stays static (vm_wait below)
       if (span2) {
         // span dword 64 j + l - sh = lane l of store j: [header A | sensors A | header B | sensors B]
-        float* const span = rowA - sh;
+        float* const span = bobs + (unsigned)k0 * (unsigned)kObsDim - sh;   // (wave-uniform)
         const float a0 = l_norm(sa.rd0), a1 = l_norm(sa.rd1), b0 = l_norm(sb.rd0), b1 = l_norm(sb.rd1);
         const bool mA = l < kHdr + sh, mB = l < 2 * kHdr + sh;
         if (l >= sh) st_obs(span + l, mA ? hv : a0);   // (lanes < sh: the previous pair's dwords)
@@ -394,30 +419,39 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
         // per-row pieces: each row's sensors in two 256-B stores and the two headers in one (a lone
         // env, odd env count: env A's row twice, identical values to identical addresses)
         {
-        float* const rowB = rowA + (hasB ? kObsDim : 0);
-        st_obs(rowA + kHdr + l, l_norm(sa.rd0));
-        st_obs(rowA + kHdr + 64 + l, l_norm(sa.rd1));
-        st_obs(rowB + kHdr + l, l_norm(hasB ? sb.rd0 : sa.rd0));
-        st_obs(rowB + kHdr + 64 + l, l_norm(hasB ? sb.rd1 : sa.rd1));
+        // dword l of env A's row.  Add, then shift: a `4 * l` here is merged with the one that phase 1's
+        // LDS set-up computes, which then stays live across the dynamics and makes them spill
+        const unsigned lo = ((unsigned)k0 * (unsigned)kObsDim + (unsigned)l) << 2;
+        float* const rowA = at_bytes(bobs, lo);
+        float* const rowB = decltype(full)::value ? rowA + kObsDim : at_bytes(bobs, lo + (hasB ? 4u * kObsDim : 0u));
+        st_obs(rowA + kHdr, l_norm(sa.rd0));
+        st_obs(rowA + kHdr + 64, l_norm(sa.rd1));
+        st_obs(rowB + kHdr, l_norm(hasB ? sb.rd0 : sa.rd0));
+        st_obs(rowB + kHdr + 64, l_norm(hasB ? sb.rd1 : sa.rd1));
         if constexpr (SPAN) {
-          const int hl = min(l, 2 * kHdr - 1);         // lanes 0..14 env A, 15..29 env B (or A again)
-          st_obs((hl >= kHdr ? rowB - kHdr : rowA) + hl, hv);
+          // (a SPAN kernel gets here with a lone env only: lanes 0..14 its header, 15..29 the same again)
+          const int hl = min(l, 2 * kHdr - 1);
+          st_obs(at_bytes(bobs, po + 4u * (unsigned)(hl >= kHdr ? hl - kHdr : hl)), hv);
         } else {
-          const int hi = hpk & 31;
-          const bool hB = ((hpk >> 16) & 1) && hasB;    // (no env B: env A's value again)
+          const int hl = min(l, 2 * kHdr - 1), hi = hl >= kHdr ? hl - kHdr : hl;   // (as in loop_setup)
           const float hc = hi == 12 ? (float)(kMaxAccU / 10.0) : hi == 14 ? (float)(kMaxAccR / 10.0) : 0.0f;
-          st_obs(rowA + (hB ? kObsDim : 0) + hi, ((hpk >> 17) & 1) ? hc : hv);
+          // (no env B: env A's value again, to env A's row)
+          const unsigned ho = (unsigned)hpk & 0x3ffu;
+          const unsigned hoA = ho - (((unsigned)hpk >> 16) & 1u) * (unsigned)(4 * kObsDim);
+          st_obs(at_bytes(bobs, po + (hasB ? ho : hoA)), ((hpk >> 17) & 1) ? hc : hv);
         }
         }
       }
-      const bool term_l = hb ? termB : sa.term;         // reward, terminated: lanes 0..31 env A,
-      const bool coll_l = hb ? collB : collA;           // 32..63 env B
-      st_out(io.rew + el, coll_l ? -20.0f + meta.x : meta.x);
-      io.term[el] = term_l;
+      // reward, terminated: lanes 0..31 env A, 32..63 env B; the two wave-uniform flags become a lane
+      // mask on the scalar unit (a per-lane select of them is three VALU instructions each)
+      const bool term_l = half_lanes(sa.term, termB);
+      const bool coll_l = half_lanes(collA, collB);
+      st_out(at_bytes(brew, 4u * kl), coll_l ? -20.0f + meta.x : meta.x);
+      *at_bytes(bterm, kl) = term_l;
       const bool done_l = term_l | ((nt >> 16) & 1);
-      if constexpr (DONE) io.done[el] = done_l;        // (>= 7 stores still follow the DMA)
-      const unsigned long long dm = ballot(done_l);
-      const bool doneA = (unsigned)dm != 0u, doneB = hasB && (unsigned)(dm >> 32) != 0u;
+      if constexpr (DONE) *at_bytes(bdone, kl) = done_l;   // (>= 7 stores still follow the DMA)
+      const BallotHalves dm = ballot_halves(ballot(done_l));
+      const bool doneA = dm.lo != 0u, doneB = hasB && dm.hi != 0u;
       if (__builtin_expect_with_probability(doneA | doneB, 0, kQRare)) {
         const QColdArgs c = q_cold_args();
         if (doneA) q_emit_done(c.S, c.io, e0, sa, recs + k0 * kQRec, rotA);
@@ -456,6 +490,8 @@ __device__ __forceinline__ void step_q_body(const State<float>& S, const IO<floa
     }
     QMARK(7);
   }
+  };
+  if ((nbe & 1) == 0) run_pairs(std::true_type{}); else run_pairs(std::false_type{});   // (wave-uniform, per block)
   QMARK(11);
   qprof_flush(qp);
 #ifdef USV_DIAG_STAMPS

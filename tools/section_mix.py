@@ -10,6 +10,8 @@ step_q_body: 10 = phase 1 (dynamics, first DMAs) up to the barrier; 0 -> 1 = pai
 next pair's DMA, span set-up); 1 -> 2 = lidar set-up (per-obstacle records, windows, prefix scan);
 2 -> 3 = the passes (marks, max-scan, pair tests, ds_min); 3 -> 4 = slot read-back; 4 -> 5 =
 stores, the next pair's record, done handling; 5 -> 6 = the vmcnt wait; 11 / 7 = same-step resets.
+The pair loop is compiled twice (full pairs only / the general body with the lone-env case): a
+marker met a second time opens a section named "<id>#2"; which copy is which shows in its counts.
 Static counts: the pass code runs 1.65 times per pair at C3 and branches run once or not at all,
 so this attributes the pipes' work to sections, it does not replace the SQ counters.
 """
@@ -48,13 +50,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernel", default=r"_ZN3usv13step_q_kernelILi0ELb1ELb0ELb1ELb0ELb0EEEv")
     ap.add_argument("--asm", default="/tmp/usv_sections.s")
+    ap.add_argument("--reuse", action="store_true", help="read the listing at --asm instead of compiling")
     args = ap.parse_args()
     src = os.path.join(ROOT, "gym-usv_amd", "csrc", "usv_kernels.hip")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S",
-                    "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-mllvm", "-disable-hoisting-to-hotter-blocks=all",
-                    "-mllvm", "-block-freq-ratio-threshold=1", "-I" + os.path.join(ROOT, "include"),
-                    "-DUSV_DIAG", "-DUSV_DIAG_SECTIONS", *os.environ.get("XDEFS", "").split(), "-o", args.asm, src], check=True,
-                   stderr=subprocess.DEVNULL)
+    if not args.reuse:
+        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-S",
+                        "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-mllvm",
+                        "-disable-hoisting-to-hotter-blocks=all", "-mllvm", "-block-freq-ratio-threshold=1",
+                        "-I" + os.path.join(ROOT, "include"), "-DUSV_DIAG", "-DUSV_DIAG_SECTIONS",
+                        *os.environ.get("XDEFS", "").split(), "-o", args.asm, src], check=True,
+                       stderr=subprocess.DEVNULL)
     t = open(args.asm).read()
     names = [n for n in re.findall(r"^(_Z\w+):", t, re.M) if re.match(args.kernel, n)]
     if not names:
@@ -64,10 +69,14 @@ def main():
     body = t[i:t.find(".Lfunc_end", i)].split("\n")
     sec = "entry"
     mix = collections.OrderedDict()
+    seen = collections.Counter()
     for line in body:
         m = re.search(r";@@QMARK (\d+)", line)
         if m:
-            sec = m.group(1)
+            # a marker met again (the pair loop exists twice: the full-pair body and the general one; 11
+            # both ends the loop and follows the resets) opens a section of its own: "1", then "1#2"
+            seen[m.group(1)] += 1
+            sec = m.group(1) if seen[m.group(1)] == 1 else f"{m.group(1)}#{seen[m.group(1)]}"
             continue
         if not line.startswith("\t") or line.strip().startswith((".", ";")):
             continue
