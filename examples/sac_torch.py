@@ -1,0 +1,269 @@
+"""Torch-native SAC on the HIP vector env with the device replay buffer: the reference's off-policy
+trainer without stable-baselines3.
+
+The reference trains ``SAC("MlpPolicy", VecFrameStack(env, 5), **config_sac)``
+(train_test/sb3_train_vec.py:58-72, train_test/config.py:17-37).  SB3 is absent from this image, so this
+is a compact SAC with config_sac's hyper-parameters where they carry over:
+
+* twin Q networks and a tanh-Gaussian actor, ``net_arch=[400, 300]``, ReLU; Polyak-averaged target
+  critics (SB3's tau 0.005); ``gamma=0.99``, ``learning_rate=1e-4``, ``batch_size=256``,
+  ``train_freq=8``, ``gradient_steps=8``, ``buffer_size=400000``, ``ent_coef='auto'`` (log-coefficient
+  learned towards the target entropy ``-act_dim``, initial value 1);
+* the frame stack and the episode statistics are ``DeviceWrappers`` (one HIP launch behind the step);
+* ``device_replay=True``: the replay buffer is ``gym_usv_amd.DeviceReplay``: one 143-float frame of obs
+  and of next_obs per transition where full storage keeps two 715-float stacks, and one launch per
+  minibatch that rebuilds both windows (``sample`` = one device ``randint`` + ``gather``);
+  ``device_replay=False``: a torch full-storage buffer (two ``[R, N, W]`` tensors, row copies to store,
+  five indexed reads to sample);
+* ``check_replay=True`` keeps both and asserts that every minibatch of the two is bitwise equal (the
+  assertion reads one flag per minibatch back to the host: a test mode).
+
+gSDE for SAC (config_sac's ``use_sde``) is out of scope: the actor's noise is torch's.  ``learning_starts``
+counts vector steps here (SB3 counts transitions: 50 000 of them are 12 steps of 4096 envs).  The loop
+collects ``train_freq`` steps, then takes ``gradient_steps`` gradient steps, as SB3's ``learn`` does.
+Whole runs of the two buffer modes are two samples of one algorithm: torch's own kernels need not be
+bitwise reproducible.
+
+    python examples/sac_torch.py --envs 4096 --steps 400 --device-replay
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "gym-usv_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import torch  # noqa: E402
+import torch.nn as nn  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+CONFIG_SAC = {"n_stack": 5, "net_arch": (400, 300), "lr": 1e-4, "gamma": 0.99, "tau": 0.005, "buffer_size": 400000,
+              "batch_size": 256, "train_freq": 8, "gradient_steps": 8, "learning_starts": 12}
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0   # SB3 sac/policies.py
+
+
+def mlp(inp, hidden, out):
+    layers, d = [], inp
+    for h in hidden:
+        layers += [nn.Linear(d, h), nn.ReLU()]
+        d = h
+    return nn.Sequential(*layers, nn.Linear(d, out))
+
+
+class Actor(nn.Module):
+    def __init__(self, obs_dim, act_dim, hidden):
+        super().__init__()
+        self.body = mlp(obs_dim, hidden[:-1], hidden[-1])
+        self.mu, self.log_std = nn.Linear(hidden[-1], act_dim), nn.Linear(hidden[-1], act_dim)
+
+    def forward(self, obs):
+        """(action in [-1, 1], its log-probability): SquashedDiagGaussianDistribution, epsilon 1e-6."""
+        h = F.relu(self.body(obs))
+        mu, log_std = self.mu(h), self.log_std(h).clamp(LOG_STD_MIN, LOG_STD_MAX)
+        std = log_std.exp()
+        u = mu + std * torch.randn_like(mu)
+        a = torch.tanh(u)
+        logp = (-0.5 * ((u - mu) / std) ** 2 - log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+        return a, logp - torch.log(1 - a * a + 1e-6).sum(-1)
+
+
+class Critic(nn.Module):
+    def __init__(self, obs_dim, act_dim, hidden):
+        super().__init__()
+        self.q1, self.q2 = mlp(obs_dim + act_dim, hidden, 1), mlp(obs_dim + act_dim, hidden, 1)
+
+    def forward(self, obs, act):
+        x = torch.cat((obs, act), -1)
+        return self.q1(x), self.q2(x)
+
+
+class TorchReplay:
+    """Full storage in torch: what a trainer writes without ``DeviceReplay``."""
+
+    def __init__(self, n, buffer_size, W, A, device):
+        self.n, self.rows = n, max(buffer_size // n, 1)
+        z = lambda *s: torch.zeros(s, device=device)    # noqa: E731
+        R = self.rows
+        self.obs, self.next_obs, self.act = z(R, n, W), z(R, n, W), z(R, n, A)
+        self.rew, self.done, self.timeout = z(R, n), z(R, n), z(R, n)
+        self.count = 0
+
+    @property
+    def size(self):
+        return min(self.count, self.rows)
+
+    def put_obs(self, stacked, action):
+        p = self.count % self.rows
+        self.obs[p], self.act[p] = stacked, action
+
+    def put_step(self, rew, term, trunc, next_stack, final_stack):
+        p = self.count % self.rows
+        done = term.bool() | trunc.bool()
+        self.next_obs[p] = torch.where(done[:, None], final_stack, next_stack)
+        self.rew[p], self.done[p] = rew.float(), done.float()
+        self.timeout[p] = (trunc.bool() & ~term.bool()).float()
+        self.count += 1
+
+    def gather(self, idx):
+        from gym_usv_amd.replay import ReplaySamples
+        W, A = self.obs.shape[-1], self.act.shape[-1]
+        dones = (self.done.reshape(-1)[idx] * (1 - self.timeout.reshape(-1)[idx])).reshape(-1, 1)
+        return ReplaySamples(self.obs.reshape(-1, W)[idx], self.act.reshape(-1, A)[idx], self.next_obs.reshape(-1, W)[idx],
+                             dones, self.rew.reshape(-1)[idx].reshape(-1, 1))
+
+
+class SAC:
+    def __init__(self, env, seed=0, device_replay=True, check_replay=False, **cfg):
+        from gym_usv_amd import DeviceReplay
+        from gym_usv_amd.wrappers import DeviceWrappers
+        self.cfg = c = dict(CONFIG_SAC, **cfg)
+        self.env, self.device = env, env.device
+        self.N, D, A, k = env.num_envs, env.obs_dim, env.act_dim, c["n_stack"]
+        W = k * D
+        torch.manual_seed(seed)
+        d = self.device
+        self.actor = Actor(W, A, c["net_arch"]).to(d)
+        self.critic, self.target = Critic(W, A, c["net_arch"]).to(d), Critic(W, A, c["net_arch"]).to(d)
+        self.target.load_state_dict(self.critic.state_dict())
+        self.log_ent = torch.zeros(1, device=d, requires_grad=True)      # ent_coef 'auto': initial value 1
+        self.target_entropy = -float(A)
+        self.opt_a = torch.optim.Adam(self.actor.parameters(), lr=c["lr"])
+        self.opt_c = torch.optim.Adam(self.critic.parameters(), lr=c["lr"])
+        self.opt_e = torch.optim.Adam([self.log_ent], lr=c["lr"])
+        lo, hi = env.single_action_space.low, env.single_action_space.high
+        self.a_lo = torch.as_tensor(lo, device=d, dtype=torch.float32)
+        self.a_hi = torch.as_tensor(hi, device=d, dtype=torch.float32)
+        self.wr = DeviceWrappers(self.N, D, k, d, env.reward.dtype)
+        self.rb = self.shadow = None
+        if device_replay or check_replay:
+            self.rb = DeviceReplay(self.N, c["buffer_size"], W, A, d, env.reward.dtype, n_stack=k)
+        if not device_replay or check_replay:
+            self.shadow = TorchReplay(self.N, c["buffer_size"], W, A, d)
+        self.device_replay = device_replay
+        obs, _ = env.reset(seed=seed)
+        self.wr.reset(obs)
+        self.env_steps = self.checked = 0
+        self._totals = (0.0, 0, 0)
+
+    @torch.no_grad()
+    def collect(self, steps, random_actions):
+        for _ in range(steps):
+            obs = self.wr.stacked                           # the ring's window, no clone
+            if random_actions:                              # SB3: uniform actions before learning_starts
+                a = torch.rand((self.N, self.a_lo.numel()), device=self.device) * 2 - 1
+            else:
+                a, _ = self.actor(obs)
+            for buf in (self.rb, self.shadow):
+                if buf is not None:
+                    buf.put_obs(obs, a)
+            a_env = self.a_lo + (a + 1) * 0.5 * (self.a_hi - self.a_lo)   # unscale_action
+            o, rew, term, trunc, info = self.env.step(a_env)
+            stacked, final_stack, _ = self.wr.step(o, rew, info["_final_obs"], info["final_obs"])
+            for buf in (self.rb, self.shadow):
+                if buf is not None:
+                    buf.put_step(rew, term, trunc, stacked, final_stack)
+            self.env_steps += self.N
+
+    def minibatch(self):
+        c = self.cfg
+        size = self.rb.size if self.rb is not None else self.shadow.size
+        idx = torch.randint(0, size * self.N, (c["batch_size"],), device=self.device)
+        mb = self.rb.gather(idx) if self.device_replay else self.shadow.gather(idx)
+        if self.rb is not None and self.shadow is not None:
+            other = self.shadow.gather(idx) if self.device_replay else self.rb.gather(idx)
+            for name, x, y in zip(mb._fields, mb, other):
+                assert x.shape == y.shape and torch.equal(x.contiguous().view(torch.int32), y.contiguous().view(torch.int32)), \
+                    f"minibatch field {name} differs between DeviceReplay and the torch buffer"
+            self.checked += 1
+        return mb
+
+    def train(self, gradient_steps):
+        c, stats = self.cfg, []
+        for _ in range(gradient_steps):
+            mb = self.minibatch()
+            a_pi, logp = self.actor(mb.observations)
+            ent = self.log_ent.detach().exp()
+            ent_loss = -(self.log_ent * (logp.detach() + self.target_entropy)).mean()
+            self.opt_e.zero_grad(set_to_none=True)
+            ent_loss.backward()
+            self.opt_e.step()
+            with torch.no_grad():
+                a2, logp2 = self.actor(mb.next_observations)
+                q_next = torch.min(*self.target(mb.next_observations, a2)) - ent * logp2[:, None]
+                target = mb.rewards + (1 - mb.dones) * c["gamma"] * q_next
+            q1, q2 = self.critic(mb.observations, mb.actions)
+            critic_loss = 0.5 * (F.mse_loss(q1, target) + F.mse_loss(q2, target))
+            self.opt_c.zero_grad(set_to_none=True)
+            critic_loss.backward()
+            self.opt_c.step()
+            q_pi = torch.min(*self.critic(mb.observations, a_pi))
+            actor_loss = (ent * logp[:, None] - q_pi).mean()
+            self.opt_a.zero_grad(set_to_none=True)
+            actor_loss.backward()
+            self.opt_a.step()
+            with torch.no_grad():                           # polyak_update
+                for p, t in zip(self.critic.parameters(), self.target.parameters()):
+                    t.mul_(1 - c["tau"]).add_(p, alpha=c["tau"])
+            stats.append(torch.stack((actor_loss.detach(), critic_loss.detach(), ent.squeeze(), ent_loss.detach())))
+        s = torch.stack(stats).mean(0).tolist()
+        return {"actor_loss": s[0], "critic_loss": s[1], "ent_coef": s[2], "ent_coef_loss": s[3]}
+
+    def episode_stats(self):
+        now, was = self.wr.totals(), self._totals
+        self._totals = now
+        eps = now[1] - was[1]
+        if eps == 0:
+            return {"episodes": 0}
+        return {"episodes": eps, "ep_rew_mean": (now[0] - was[0]) / eps, "ep_len_mean": (now[2] - was[2]) / eps}
+
+
+def train(env_id="usv-simple", envs=4096, steps=400, seed=0, log=print, device_replay=True, check_replay=False,
+          max_episode_steps=None, **cfg):
+    """``steps`` vector steps of ``envs`` envs.  Returns one record per training round (``train_freq``
+    steps, then ``gradient_steps`` gradient steps once ``learning_starts`` steps are in the buffer)."""
+    import gym_usv_amd
+    kw = {} if max_episode_steps is None else {"max_episode_steps": max_episode_steps}
+    env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False, **kw)
+    sac = SAC(env, seed=seed, device_replay=device_replay, check_replay=check_replay, **cfg)
+    c, hist, done_steps = sac.cfg, [], 0
+    t0 = time.perf_counter()
+    while done_steps < steps:
+        block = min(c["train_freq"], steps - done_steps)
+        sac.collect(block, random_actions=done_steps < c["learning_starts"])
+        done_steps += block
+        if done_steps <= c["learning_starts"]:
+            continue
+        rec = {"step": done_steps, **sac.train(c["gradient_steps"]), "gradient_steps": c["gradient_steps"],
+               **sac.episode_stats(), "env_steps": sac.env_steps, "minibatches_checked": sac.checked}
+        torch.cuda.synchronize()
+        rec["wall_s"] = round(time.perf_counter() - t0, 3)
+        hist.append(rec)
+        log(json.dumps(rec))
+    env.close()
+    return hist
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--env-id", default="usv-simple")
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--buffer-size", type=int, default=CONFIG_SAC["buffer_size"])
+    ap.add_argument("--batch-size", type=int, default=CONFIG_SAC["batch_size"])
+    ap.add_argument("--device-replay", action="store_true", help="DeviceReplay instead of the torch full-storage buffer")
+    ap.add_argument("--check-replay", action="store_true", help="keep both buffers and compare every minibatch bitwise")
+    a = ap.parse_args()
+    train(a.env_id, a.envs, a.steps, a.seed, device_replay=a.device_replay, check_replay=a.check_replay,
+          buffer_size=a.buffer_size, batch_size=a.batch_size)
+
+
+if __name__ == "__main__":
+    main()

@@ -25,6 +25,8 @@
 //   usv_rollout_frames.hpp  frame store and minibatch gather (usv_rollout_put_obs_frames / usv_rollout_gather)
 //   usv_sde_math.hpp      gSDE head: Philox numbering, Box-Muller, sums, clip, log-probability (host C++, no HIP)
 //   usv_sde.hpp           fused gSDE action head (usv_sde_sample / usv_sde_weights)
+//   usv_replay_math.hpp   replay buffer: slots, frame rows, age and live masks (host C++, no HIP)
+//   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -53,6 +55,7 @@
 #include "usv_rollout.hpp"
 #include "usv_rollout_frames.hpp"
 #include "usv_sde.hpp"
+#include "usv_replay.hpp"        // (last: every kernel before it keeps its place in the code object)
 
 // ============================================================================= host side
 using namespace usv;
@@ -1286,6 +1289,103 @@ int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std, float* w
     hipLaunchKernelGGL(sde_weights_kernel<1>, grid, block, 0, (hipStream_t)stream, a, std, w);
   else
     hipLaunchKernelGGL(sde_weights_kernel<2>, grid, block, 0, (hipStream_t)stream, a, std, w);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- device replay buffer (usv_replay.hpp)
+// The checks that need no HIP call, then the device of every buffer (`more`: the call's own); fills the
+// kernels' arguments.
+static int replay_args(const usv_replay* rp, Bufs more, RpArgs& a, int& dev) {
+  if (!rp) return fail(USV_ERR_ARG, "null usv_replay");
+  if (rp->n <= 0 || rp->rows <= 0 || rp->obs_width <= 0 || rp->act_dim <= 0)
+    return fail(USV_ERR_ARG, "usv_replay: n, rows, obs_width and act_dim must be > 0");
+  if (rp->k < 1 || rp->k > kRfMaxStack || rp->d < 1) return fail(USV_ERR_ARG, "usv_replay: k must be in [1, 32] and d >= 1");
+  if ((int64_t)rp->k * rp->d != (int64_t)rp->obs_width) return fail(USV_ERR_ARG, "usv_replay: k * d must equal obs_width");
+  if ((rp->flags & ~USV_REPLAY_CLEAR_KEEPS_SIGN) != 0 || rp->reserved != 0) return fail(USV_ERR_ARG, "usv_replay: unknown flags");
+  if (rp_frame_rows(rp->rows, rp->k) > 2147483647) return fail(USV_ERR_ARG, "usv_replay: rows + k - 1 must be below 2^31");
+  Buf all[kMaxBufs] = {{rp->frames, 4}, {rp->next_frame, 4}, {rp->act, 4},     {rp->rew, 4},      {rp->done, 1},
+                       {rp->timeout, 1}, {rp->age, 1},       {rp->age_now, 1}, {rp->bad_count, 4}};
+  size_t nb = 9;
+  switch (check_bufs(all, nb)) {
+    case kBufNull: return fail(USV_ERR_ARG, "usv_replay: null buffer");
+    case kBufAlign: return fail(USV_ERR_ARG, "usv_replay: a buffer is not aligned to its element size");
+    default: break;
+  }
+  for (const Buf& b : more) all[nb++] = b;
+  switch (check_bufs(all, nb, &dev)) {
+    case kBufNull: return fail(USV_ERR_ARG, "usv_replay: null argument");
+    case kBufAlign: return fail(USV_ERR_ARG, "usv_replay: an argument is not aligned to its element size");
+    case kBufDevice:
+      return fail(USV_ERR_ARG, dev < 0 ? "usv_replay: frames is not a device pointer"
+                                       : "usv_replay: a buffer is not a device pointer on the device that holds frames");
+    case kBufOk: break;
+  }
+  a = RpArgs{rp->n, rp->rows, rp->obs_width, rp->act_dim, rp->k, rp->d, rp->flags & USV_REPLAY_CLEAR_KEEPS_SIGN,
+             (int)rp_frame_rows(rp->rows, rp->k), rp->frames, rp->next_frame, rp->act, rp->rew, rp->done, rp->timeout,
+             rp->age, rp->age_now, rp->bad_count};
+  return USV_OK;
+}
+
+int usv_replay_put_obs(const usv_replay* rp, int64_t c, const float* stacked, size_t stride, const float* act,
+                       void* stream) {
+  RpArgs a;
+  int dev;
+  if (c < 0) return fail(USV_ERR_ARG, "usv_replay_put_obs: the step number c must be >= 0");
+  if (rp && rp->obs_width > 0 && stride < (size_t)rp->obs_width)
+    return fail(USV_ERR_ARG, "usv_replay_put_obs: the row stride is below obs_width");
+  if (int rc = replay_args(rp, {{stacked, 4}, {act, 4}}, a, dev)) return rc;
+  DeviceGuard g(dev);
+  hipLaunchKernelGGL(replay_obs_kernel, wrap_grid(a.n), dim3(kBlock), 0, (hipStream_t)stream, a, (int)rp_slot(c, a.R),
+                     (int)rp_frame_row(c, a.P), (int)(c == 0), stacked, stride, act);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_replay_put_step(const usv_replay* rp, int64_t c, const void* rew, int32_t reward_bytes, const uint8_t* term,
+                        const uint8_t* trunc, const float* next_stacked, size_t next_stride, const float* final_stack,
+                        void* stream) {
+  RpArgs a;
+  int dev;
+  if (c < 0) return fail(USV_ERR_ARG, "usv_replay_put_step: the step number c must be >= 0");
+  if (reward_bytes != 4 && reward_bytes != 8) return fail(USV_ERR_ARG, "usv_replay_put_step: reward_bytes must be 4 or 8");
+  if (rp && rp->obs_width > 0 && next_stride < (size_t)rp->obs_width)
+    return fail(USV_ERR_ARG, "usv_replay_put_step: the row stride is below obs_width");
+  if (int rc = replay_args(rp, {{rew, (uintptr_t)reward_bytes}, {term, 1}, {trunc, 1}, {next_stacked, 4}, {final_stack, 4}},
+                           a, dev))
+    return rc;
+  DeviceGuard g(dev);
+  const hipStream_t s = (hipStream_t)stream;
+  const dim3 grid = wrap_grid(a.n), block(kBlock);
+  const int slot = rp_slot(c, a.R);
+  if (reward_bytes == 8)
+    hipLaunchKernelGGL(replay_step_kernel<double>, grid, block, 0, s, a, slot, (const double*)rew, term, trunc, next_stacked,
+                       next_stride, final_stack);
+  else
+    hipLaunchKernelGGL(replay_step_kernel<float>, grid, block, 0, s, a, slot, (const float*)rew, term, trunc, next_stacked,
+                       next_stride, final_stack);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_replay_gather(const usv_replay* rp, int64_t count, const int64_t* idx, int32_t B, float* obs_out, float* act_out,
+                      float* next_obs_out, float* done_out, float* rew_out, void* stream) {
+  RpArgs a;
+  int dev;
+  if (count < 0) return fail(USV_ERR_ARG, "usv_replay_gather: count must be >= 0");
+  if (B <= 0) return fail(USV_ERR_ARG, "usv_replay_gather: B must be > 0");
+  if (!idx) return fail(USV_ERR_ARG, "usv_replay_gather: null idx");
+  const Bufs more = {{idx, 8}, {obs_out, 4}, {act_out, 4}, {next_obs_out, 4}, {done_out, 4}, {rew_out, 4}};
+  const BufFault of = check_bufs(more.begin() + 1, 5);  // the outputs
+  if (of == kBufNull) return fail(USV_ERR_ARG, "usv_replay_gather: null output");
+  if ((reinterpret_cast<uintptr_t>(idx) & 7) != 0) return fail(USV_ERR_ARG, "usv_replay_gather: idx is not 8-B aligned");
+  if (of == kBufAlign) return fail(USV_ERR_ARG, "usv_replay_gather: an output is not 4-B aligned");
+  if (int rc = replay_args(rp, more, a, dev)) return rc;
+  DeviceGuard g(dev);
+  const int per_block = kWaves * kRpRows;
+  const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
+  hipLaunchKernelGGL(replay_gather_kernel, grid, block, 0, (hipStream_t)stream, a, rp_laps(count, a.R, a.k),
+                     (long long)rp_size(count, a.R), idx, (int)B, obs_out, act_out, next_obs_out, done_out, rew_out);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

@@ -109,6 +109,19 @@ class UsvSde(ctypes.Structure):
                 ("low", ctypes.c_float * 4), ("high", ctypes.c_float * 4)]
 
 
+REPLAY_CLEAR_KEEPS_SIGN = 1
+
+
+class UsvReplay(ctypes.Structure):
+    """usv_replay: the caller-owned device buffers of the replay buffer (usv_replay_put_obs / _put_step / _gather)."""
+    _fields_ = [("n", ctypes.c_int32), ("rows", ctypes.c_int32), ("obs_width", ctypes.c_int32),
+                ("act_dim", ctypes.c_int32), ("k", ctypes.c_int32), ("d", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("frames", ctypes.c_void_p), ("next_frame", ctypes.c_void_p),
+                ("act", ctypes.c_void_p), ("rew", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("timeout", ctypes.c_void_p), ("age", ctypes.c_void_p), ("age_now", ctypes.c_void_p),
+                ("bad_count", ctypes.c_void_p)]
+
+
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
 _i64, _u32 = ctypes.c_int64, ctypes.c_uint32
@@ -159,6 +172,9 @@ SIGNATURES = [
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
     ("usv_sde_sample", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("usv_sde_weights", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _vp]),
+    ("usv_replay_put_obs", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _sz, _vp, _vp]),
+    ("usv_replay_put_step", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _vp]),
+    ("usv_replay_gather", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _LIBS = {}

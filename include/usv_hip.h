@@ -551,6 +551,77 @@ int usv_sde_sample(const usv_sde* s, uint32_t epoch, const float* mean_dev, cons
                    float* logp_dev, void* stream);
 int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std_dev, float* w_dev, void* stream);
 
+/* Device replay buffer: SB3's ReplayBuffer (common/buffers.py: add, sample, _get_samples with
+ * optimize_memory_usage=False and handle_timeout_termination=True) and the terminal-observation
+ * substitution of OffPolicyAlgorithm._store_transition, for windows of k frames of d floats that evolve by
+ * the VecFrameStack rule (usv_wrap_step).  It keeps one frame of obs and one of next_obs per transition
+ * where SB3 keeps two k d stacks.  Handle-free and stream-ordered like usv_rollout_*; additive (ABI v5
+ * addition).  No host sync: the ring position is the caller's (SB3's pos / full), passed as the 64-bit
+ * step number c = 0, 1, .. of the call (counted since the buffers were new or the caller started over)
+ * and, to the gather, as count = the number of completed transitions.  tests/replay_ref.py restates the
+ * full-storage buffer; every gathered output equals it bit for bit.
+ *
+ * The ring has rows = R transitions per env (SB3: buffer_size // n_envs); transition c lives in slot
+ * c % R.  frames is [n][R + k - 1][d], env-major: the frame of step c is row c mod (R + k - 1), the k - 1
+ * older frames of the first window are rows R .. R + k - 2.  next_frame is [R][n][d], act [R][n][act_dim],
+ * rew [R][n] float32, done / timeout / age [R][n] uint8, age_now [n] uint8 (the caller sets it to k - 1
+ * before step 0).  csrc/usv_replay_math.hpp holds the arithmetic.
+ *
+ * usv_replay_put_obs(rp, c, stacked, row stride, act), before env step c      <- add: observations, actions
+ *   stores the newest d columns of each stacked row [k d] (any 4-B-aligned base, row stride >= k d floats:
+ *   DeviceWrappers.stacked is read in place) as the frame of step c (at c == 0 the whole window: the
+ *   older columns go to the prologue rows as they are, cleared slots included), act[slot] = act_dev
+ *   [n][act_dim] and age[slot] = age_now.
+ * usv_replay_put_step(rp, c, rew, reward_bytes, term, trunc, next_stacked, row stride, final_stack), after
+ * env step c:                                                  <- add: rewards, dones, timeouts, next_obs
+ *   rew[slot] = float32(reward); done[slot] = term | trunc; timeout[slot] = trunc & !term (the adapter's
+ *   TimeLimit.truncated); next_frame[slot] = the newest d columns of final_stack [n][k d] (usv_wrap_step's)
+ *   for a done env (_store_transition: next_obs = terminal_observation) and of next_stacked, the window
+ *   after the step, otherwise (only those rows of either are read); age_now = 0 for a done env, else
+ *   min(age_now + 1, k - 1).
+ * usv_replay_gather(rp, count, idx_dev [B] int64, B, out...): for i = idx[b] = slot * n + e with slot in
+ * [0, min(count, R)), one launch writes                                       <- _get_samples
+ *   obs_out[b] [k d]: the stacked window of that transition; next_obs_out[b] [k d]: its next_obs;
+ *   act_out[b] [act_dim]; done_out[b] = float32(done) * (1 - float32(timeout)); rew_out[b].
+ *   Slot j of obs (0 = oldest) is live when j >= k - 1 - age, slot j of next_obs when slot j + 1 of obs is
+ *   (its newest always); a cleared element is +0.0, or x * 0.0f with USV_REPLAY_CLEAR_KEEPS_SIGN.
+ *   An idx outside [0, min(count, R) * n) is not dereferenced: its outputs are NaN and *bad_count is
+ *   incremented (never reset by the library); the call still returns USV_OK.
+ * Preconditions the library cannot check: the calls of a run pass c = 0, 1, .. with put_obs(c) before
+ * put_step(c); the windows evolve by the VecFrameStack rule with exactly the dones given (a window reset
+ * by hand between stores is not supported: start over at c = 0 with age_now = k - 1); and no gather runs
+ * between put_obs(c) and put_step(c): the frame row just written is the one the oldest valid window
+ * still needs.
+ *
+ * USV_ERR_ARG, before any HIP call, for a NULL usv_replay, n / rows / obs_width / act_dim <= 0, k outside
+ * [1, 32], d < 1, k * d != obs_width, unknown flags or reserved != 0, a NULL buffer or one not aligned to
+ * its element size, c < 0 or count < 0, a row stride below obs_width, reward_bytes not 4 / 8, B <= 0, a
+ * NULL idx (or one not 8-B aligned) or output.  Then for a buffer that is not device memory of the device
+ * that holds frames. */
+#define USV_REPLAY_CLEAR_KEEPS_SIGN 1
+typedef struct usv_replay {    /* caller-owned device buffers */
+  int32_t n, rows, obs_width, act_dim;
+  int32_t k, d;                /* n_stack and floats per frame; k * d == obs_width */
+  int32_t flags;               /* USV_REPLAY_* */
+  int32_t reserved;            /* 0 */
+  float* frames;               /* [n][rows + k - 1][d] */
+  float* next_frame;           /* [rows][n][d] */
+  float* act;                  /* [rows][n][act_dim] */
+  float* rew;                  /* [rows][n] */
+  uint8_t* done;               /* [rows][n] */
+  uint8_t* timeout;            /* [rows][n] */
+  uint8_t* age;                /* [rows][n] */
+  uint8_t* age_now;            /* [n] */
+  int32_t* bad_count;          /* [1] indices the gather refused */
+} usv_replay;
+int usv_replay_put_obs(const usv_replay* rp, int64_t c, const float* stacked_dev, size_t row_stride_floats,
+                       const float* act_dev, void* stream);
+int usv_replay_put_step(const usv_replay* rp, int64_t c, const void* rew_dev, int32_t reward_bytes,
+                        const uint8_t* term_dev, const uint8_t* trunc_dev, const float* next_stacked_dev,
+                        size_t next_row_stride_floats, const float* final_stack_dev, void* stream);
+int usv_replay_gather(const usv_replay* rp, int64_t count, const int64_t* idx_dev, int32_t B, float* obs_out,
+                      float* act_out, float* next_obs_out, float* done_out, float* rew_out, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
