@@ -18,13 +18,21 @@ is a compact SAC with config_sac's hyper-parameters where they carry over:
 * ``check_replay=True`` keeps both and asserts that every minibatch of the two is bitwise equal (the
   assertion reads one flag per minibatch back to the host: a test mode).
 
-gSDE for SAC (config_sac's ``use_sde``) is out of scope: the actor's noise is torch's.  ``learning_starts``
-counts vector steps here (SB3 counts transitions: 50 000 of them are 12 steps of 4096 envs).  The loop
+* ``sde_kernel=True`` (``--sde-kernel``): config_sac's ``use_sde=True``, ``sde_sample_freq=4``,
+  ``log_std_init=-3`` through ``gym_usv_amd.DeviceSDE.squashed`` (one HIP launch forward, two backward, no
+  exploration matrix in memory): the actor's ``log_std`` is a ``[300, 2]`` parameter, ``mu`` passes through
+  ``hardtanh(+-2)`` (SB3's ``clip_mean``), one head of ``envs`` rows collects with a new noise epoch every
+  fourth step and its ``env_actions`` feed ``env.step``, and a second head of ``batch_size`` rows with another
+  seed serves both actor calls of a gradient step under one epoch, as ``SAC.train``'s ``reset_noise`` does.
+  Without it the actor's noise is torch's (a state-independent tanh-Gaussian) and nothing here changes.
+
+``learning_starts`` counts vector steps here (SB3 counts transitions: 50 000 of them are 12 steps of 4096 envs).  The loop
 collects ``train_freq`` steps, then takes ``gradient_steps`` gradient steps, as SB3's ``learn`` does.
 Whole runs of the two buffer modes are two samples of one algorithm: torch's own kernels need not be
 bitwise reproducible.
 
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay
+    python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel
 """
 from __future__ import annotations
 
@@ -45,8 +53,10 @@ import torch.nn as nn  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 CONFIG_SAC = {"n_stack": 5, "net_arch": (400, 300), "lr": 1e-4, "gamma": 0.99, "tau": 0.005, "buffer_size": 400000,
-              "batch_size": 256, "train_freq": 8, "gradient_steps": 8, "learning_starts": 12}
+              "batch_size": 256, "train_freq": 8, "gradient_steps": 8, "learning_starts": 12,
+              "sde_sample_freq": 4, "log_std_init": -3.0}             # the last two: sde_kernel=True only
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0   # SB3 sac/policies.py
+CLIP_MEAN = 2.0                         # SB3 sac/policies.py, with use_sde
 
 
 def mlp(inp, hidden, out):
@@ -58,10 +68,20 @@ def mlp(inp, hidden, out):
 
 
 class Actor(nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden):
+    def __init__(self, obs_dim, act_dim, hidden, sde_log_std_init=None):
         super().__init__()
         self.body = mlp(obs_dim, hidden[:-1], hidden[-1])
-        self.mu, self.log_std = nn.Linear(hidden[-1], act_dim), nn.Linear(hidden[-1], act_dim)
+        if sde_log_std_init is None:
+            self.mu, self.log_std = nn.Linear(hidden[-1], act_dim), nn.Linear(hidden[-1], act_dim)
+        else:                                               # gSDE: log_std [latent, act_dim] is a parameter
+            self.mu = nn.Linear(hidden[-1], act_dim)
+            self.log_std = nn.Parameter(torch.full((hidden[-1], act_dim), float(sde_log_std_init)))
+
+    def sde(self, obs, head):
+        """gSDE through ``head.squashed``: its ``SquashedSample`` (actions in [-1, 1], Box actions,
+        log-probability, Gaussian actions).  StateDependentNoiseDistribution, squash_output, learn_features."""
+        h = F.relu(self.body(obs))
+        return head.squashed(F.hardtanh(self.mu(h), -CLIP_MEAN, CLIP_MEAN), h, self.log_std.exp())
 
     def forward(self, obs):
         """(action in [-1, 1], its log-probability): SquashedDiagGaussianDistribution, epsilon 1e-6."""
@@ -120,8 +140,8 @@ class TorchReplay:
 
 
 class SAC:
-    def __init__(self, env, seed=0, device_replay=True, check_replay=False, **cfg):
-        from gym_usv_amd import DeviceReplay
+    def __init__(self, env, seed=0, device_replay=True, check_replay=False, sde_kernel=False, **cfg):
+        from gym_usv_amd import DeviceReplay, DeviceSDE
         from gym_usv_amd.wrappers import DeviceWrappers
         self.cfg = c = dict(CONFIG_SAC, **cfg)
         self.env, self.device = env, env.device
@@ -129,7 +149,7 @@ class SAC:
         W = k * D
         torch.manual_seed(seed)
         d = self.device
-        self.actor = Actor(W, A, c["net_arch"]).to(d)
+        self.actor = Actor(W, A, c["net_arch"], c["log_std_init"] if sde_kernel else None).to(d)
         self.critic, self.target = Critic(W, A, c["net_arch"]).to(d), Critic(W, A, c["net_arch"]).to(d)
         self.target.load_state_dict(self.critic.state_dict())
         self.log_ent = torch.zeros(1, device=d, requires_grad=True)      # ent_coef 'auto': initial value 1
@@ -140,6 +160,11 @@ class SAC:
         lo, hi = env.single_action_space.low, env.single_action_space.high
         self.a_lo = torch.as_tensor(lo, device=d, dtype=torch.float32)
         self.a_hi = torch.as_tensor(hi, device=d, dtype=torch.float32)
+        self.head_env = self.head_mb = None
+        if sde_kernel:      # rows = global env ids / positions in the minibatch; seeds other than the env's
+            self.head_env = DeviceSDE(self.N, c["net_arch"][-1], A, d, seed + 1, lo, hi)
+            self.head_mb = DeviceSDE(c["batch_size"], c["net_arch"][-1], A, d, seed + 2, lo, hi)
+        self.sde_steps = 0
         self.wr = DeviceWrappers(self.N, D, k, d, env.reward.dtype)
         self.rb = self.shadow = None
         if device_replay or check_replay:
@@ -156,14 +181,22 @@ class SAC:
     def collect(self, steps, random_actions):
         for _ in range(steps):
             obs = self.wr.stacked                           # the ring's window, no clone
+            a_env = None
             if random_actions:                              # SB3: uniform actions before learning_starts
                 a = torch.rand((self.N, self.a_lo.numel()), device=self.device) * 2 - 1
+            elif self.head_env is not None:
+                if self.sde_steps % self.cfg["sde_sample_freq"] == 0:
+                    self.head_env.reset_noise()
+                self.sde_steps += 1
+                s = self.actor.sde(obs, self.head_env)      # the head's buffers: consumed before its next call
+                a, a_env = s.actions, s.env_actions
             else:
                 a, _ = self.actor(obs)
             for buf in (self.rb, self.shadow):
                 if buf is not None:
                     buf.put_obs(obs, a)
-            a_env = self.a_lo + (a + 1) * 0.5 * (self.a_hi - self.a_lo)   # unscale_action
+            if a_env is None:
+                a_env = self.a_lo + (a + 1) * 0.5 * (self.a_hi - self.a_lo)   # unscale_action
             o, rew, term, trunc, info = self.env.step(a_env)
             stacked, final_stack, _ = self.wr.step(o, rew, info["_final_obs"], info["final_obs"])
             for buf in (self.rb, self.shadow):
@@ -184,18 +217,27 @@ class SAC:
             self.checked += 1
         return mb
 
+    def policy(self, obs):
+        """(action, log-probability) of the update's actor calls."""
+        if self.head_mb is None:
+            return self.actor(obs)
+        s = self.actor.sde(obs, self.head_mb)
+        return s.actions, s.log_prob
+
     def train(self, gradient_steps):
         c, stats = self.cfg, []
         for _ in range(gradient_steps):
             mb = self.minibatch()
-            a_pi, logp = self.actor(mb.observations)
+            if self.head_mb is not None:
+                self.head_mb.reset_noise()                  # SAC.train: one matrix per gradient step
+            a_pi, logp = self.policy(mb.observations)
             ent = self.log_ent.detach().exp()
             ent_loss = -(self.log_ent * (logp.detach() + self.target_entropy)).mean()
             self.opt_e.zero_grad(set_to_none=True)
             ent_loss.backward()
             self.opt_e.step()
             with torch.no_grad():
-                a2, logp2 = self.actor(mb.next_observations)
+                a2, logp2 = self.policy(mb.next_observations)
                 q_next = torch.min(*self.target(mb.next_observations, a2)) - ent * logp2[:, None]
                 target = mb.rewards + (1 - mb.dones) * c["gamma"] * q_next
             q1, q2 = self.critic(mb.observations, mb.actions)
@@ -213,7 +255,12 @@ class SAC:
                     t.mul_(1 - c["tau"]).add_(p, alpha=c["tau"])
             stats.append(torch.stack((actor_loss.detach(), critic_loss.detach(), ent.squeeze(), ent_loss.detach())))
         s = torch.stack(stats).mean(0).tolist()
-        return {"actor_loss": s[0], "critic_loss": s[1], "ent_coef": s[2], "ent_coef_loss": s[3]}
+        out = {"actor_loss": s[0], "critic_loss": s[1], "ent_coef": s[2], "ent_coef_loss": s[3]}
+        if self.head_mb is not None:                        # of the round's last gradient step
+            ls = self.actor.log_std
+            out["log_std_mean"], out["log_std_move_abs_max"], out["log_std_grad_abs_max"] = torch.stack(
+                (ls.detach().mean(), (ls.detach() - c["log_std_init"]).abs().max(), ls.grad.abs().max())).tolist()
+        return out
 
     def episode_stats(self):
         now, was = self.wr.totals(), self._totals
@@ -225,13 +272,13 @@ class SAC:
 
 
 def train(env_id="usv-simple", envs=4096, steps=400, seed=0, log=print, device_replay=True, check_replay=False,
-          max_episode_steps=None, **cfg):
+          max_episode_steps=None, sde_kernel=False, **cfg):
     """``steps`` vector steps of ``envs`` envs.  Returns one record per training round (``train_freq``
     steps, then ``gradient_steps`` gradient steps once ``learning_starts`` steps are in the buffer)."""
     import gym_usv_amd
     kw = {} if max_episode_steps is None else {"max_episode_steps": max_episode_steps}
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False, **kw)
-    sac = SAC(env, seed=seed, device_replay=device_replay, check_replay=check_replay, **cfg)
+    sac = SAC(env, seed=seed, device_replay=device_replay, check_replay=check_replay, sde_kernel=sde_kernel, **cfg)
     c, hist, done_steps = sac.cfg, [], 0
     t0 = time.perf_counter()
     while done_steps < steps:
@@ -260,9 +307,10 @@ def main():
     ap.add_argument("--batch-size", type=int, default=CONFIG_SAC["batch_size"])
     ap.add_argument("--device-replay", action="store_true", help="DeviceReplay instead of the torch full-storage buffer")
     ap.add_argument("--check-replay", action="store_true", help="keep both buffers and compare every minibatch bitwise")
+    ap.add_argument("--sde-kernel", action="store_true", help="gSDE (config_sac's use_sde) through DeviceSDE.squashed")
     a = ap.parse_args()
     train(a.env_id, a.envs, a.steps, a.seed, device_replay=a.device_replay, check_replay=a.check_replay,
-          buffer_size=a.buffer_size, batch_size=a.batch_size)
+          sde_kernel=a.sde_kernel, buffer_size=a.buffer_size, batch_size=a.batch_size)
 
 
 if __name__ == "__main__":

@@ -24,7 +24,7 @@
 //   usv_rollout_frames_math.hpp  frame-deduplicated obs storage: rows, live mask, clear rule (host C++, no HIP)
 //   usv_rollout_frames.hpp  frame store and minibatch gather (usv_rollout_put_obs_frames / usv_rollout_gather)
 //   usv_sde_math.hpp      gSDE head: Philox numbering, Box-Muller, sums, clip, log-probability (host C++, no HIP)
-//   usv_sde.hpp           fused gSDE action head (usv_sde_sample / usv_sde_weights)
+//   usv_sde.hpp           fused gSDE action head (usv_sde_sample / usv_sde_weights / usv_sde_squash_forward / _backward)
 //   usv_replay_math.hpp   replay buffer: slots, frame rows, age and live masks (host C++, no HIP)
 //   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
@@ -1289,6 +1289,69 @@ int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std, float* w
     hipLaunchKernelGGL(sde_weights_kernel<1>, grid, block, 0, (hipStream_t)stream, a, std, w);
   else
     hipLaunchKernelGGL(sde_weights_kernel<2>, grid, block, 0, (hipStream_t)stream, a, std, w);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_sde_squash_forward(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
+                           const float* std, float* act, float* act_env, float* logp, float* gauss, float* var,
+                           void* stream) {
+  SdeArgs a;
+  int dev;
+  if (int rc = sde_check(s, a)) return rc;
+  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
+    return fail(USV_ERR_ARG, "usv_sde_squash_forward: the row stride must be a multiple of 4 and >= latent_dim");
+  if ((gauss == nullptr) != (var == nullptr))
+    return fail(USV_ERR_ARG, "usv_sde_squash_forward: gauss and var must be both NULL or both set");
+  const Buf all[] = {{lat, 16}, {mean, 4}, {std, 4}, {act, 4}, {act_env, 4}, {logp, 4}, {gauss, 4, true}, {var, 4, true}};
+  if (int rc = sde_bufs(all, 8, dev)) return rc;
+  a.epoch = epoch;
+  DeviceGuard g(dev);
+  const dim3 grid((unsigned)(((int64_t)a.n + kWaves - 1) / kWaves)), block(kBlock);
+  if (s->act_dim == 1)
+    hipLaunchKernelGGL(sde_squash_forward_kernel<1>, grid, block, 0, (hipStream_t)stream, a, mean, lat, stride, std, act,
+                       act_env, logp, gauss, var);
+  else
+    hipLaunchKernelGGL(sde_squash_forward_kernel<2>, grid, block, 0, (hipStream_t)stream, a, mean, lat, stride, std, act,
+                       act_env, logp, gauss, var);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+size_t usv_sde_squash_scratch_floats(const usv_sde* s) {
+  SdeArgs a;
+  if (sde_check(s, a)) return 0;
+  return (size_t)sde_partials(a.n) * (size_t)a.L * (size_t)s->act_dim;
+}
+
+int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
+                            const float* std, const float* gauss, const float* var, const float* g_act,
+                            const float* g_logp, float* g_mean, float* g_lat, size_t g_stride, float* g_std,
+                            float* scratch, void* stream) {
+  SdeArgs a;
+  int dev;
+  if (int rc = sde_check(s, a)) return rc;
+  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
+    return fail(USV_ERR_ARG, "usv_sde_squash_backward: the row stride must be a multiple of 4 and >= latent_dim");
+  if (g_stride < (size_t)s->latent_dim || g_stride % 4 != 0)
+    return fail(USV_ERR_ARG, "usv_sde_squash_backward: the g_lat row stride must be a multiple of 4 and >= latent_dim");
+  if (!scratch) return fail(USV_ERR_ARG, "usv_sde_squash_backward: null scratch");
+  const Buf all[] = {{lat, 16},  {g_lat, 16}, {scratch, 16},      {mean, 4},           {std, 4},   {gauss, 4},
+                     {var, 4},   {g_mean, 4}, {g_act, 4, true},   {g_logp, 4, true},   {g_std, 4}};
+  if (int rc = sde_bufs(all, 11, dev)) return rc;
+  a.epoch = epoch;
+  DeviceGuard g(dev);
+  const int R = (int)sde_rows_per_partial(a.n), P = (int)sde_partials(a.n), LA = a.L * s->act_dim;
+  const dim3 grid((unsigned)((P + kWaves - 1) / kWaves)), block(kBlock);
+  if (s->act_dim == 1)
+    hipLaunchKernelGGL(sde_squash_backward_kernel<1>, grid, block, 0, (hipStream_t)stream, a, R, mean, lat, stride, std,
+                       gauss, var, g_act, g_logp, g_mean, g_lat, g_stride, scratch);
+  else
+    hipLaunchKernelGGL(sde_squash_backward_kernel<2>, grid, block, 0, (hipStream_t)stream, a, R, mean, lat, stride, std,
+                       gauss, var, g_act, g_logp, g_mean, g_lat, g_stride, scratch);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(sde_std_finalise_kernel, dim3((unsigned)((LA + 15) / 16)), block, 0, (hipStream_t)stream, P, LA,
+                     scratch, g_std);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

@@ -10,6 +10,9 @@
 //                          tail and the stores.  The matrix never reaches memory.
 //   sde_weights_kernel<A>  a lane per block of four elements: w[e][j][k], SB3's exploration_mat, for
 //                          inspection, tests and checkpoints.
+//   sde_squash_forward_kernel<A>, sde_squash_backward_kernel<A>, sde_std_finalise_kernel
+//                          SAC's squashed head (usv_sde_squash_forward / _backward): the same row sums with a
+//                          tanh tail, and its gradients with the normals rebuilt, not saved; see at each.
 // The [L][A] std table is read once per wave, straight into registers: each element is used by one lane
 // of the wave, once, so staging it in LDS would add a write, a barrier and a read without saving a load;
 // the table (2 KiB at L = 256, A = 2) stays in L2 for the waves of the other envs.
@@ -88,6 +91,152 @@ __global__ __launch_bounds__(kBlock) void sde_sample_kernel(SdeArgs a, const flo
     lp = lp + sde_logp_term(ak, m, var[k]);
   }
   logp[e] = lp;
+}
+
+// sde_sample_kernel's pass loop and its 2 A wave reductions for the squashed forward: noise_k and var_k of one
+// row, wave-uniform.  A copy and not a function the two share: with the loop in a function sde_sample_kernel's
+// register allocation changes (38 VGPRs for 36 at A = 2), and that kernel's code stays as it is.
+template <int A>
+__device__ __forceinline__ void sde_row_sums(const SdeArgs& a, int l, uint64_t gid, const float* __restrict__ row,
+                                             const float* __restrict__ std, float (&noise)[A], float (&var)[A]) {
+#pragma unroll
+  for (int k = 0; k < A; ++k) noise[k] = var[k] = 0.0f;
+  for (int j0 = kSdePerLane * l; j0 < a.L; j0 += kSdePass) {
+    const float4 lv = *reinterpret_cast<const float4*>(row + j0);     // row and stride are 16-B aligned
+    const float x[4] = {lv.x, lv.y, lv.z, lv.w};
+    float s[4 * A];
+#pragma unroll
+    for (int i = 0; i < 4 * A; ++i) s[i] = std[(size_t)j0 * A + i];
+#pragma unroll
+    for (int m = 0; m < A; ++m) {
+      uint32_t o[4];
+      float z[4];
+      sde_block(a.seed, gid, a.epoch, (uint32_t)(j0 / 4) * A + m, o);
+      sde_normals(o, z);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = 4 * m + q;                        // element i of the lane's 4 A: latent i / A, action i % A
+        sde_accum(x[i / A], s[i], sde_weight(s[i], z[q]), noise[i % A], var[i % A]);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < A; ++k) {
+    noise[k] = sde_wave_sum(noise[k]);
+    var[k] = sde_wave_sum(var[k]);
+  }
+}
+
+// The squashed head's forward: the same row sums, then lane 0's tail.  gauss and var (the backward's saved
+// u and var_k) are NULL together on a call that will not be differentiated.
+template <int A>
+__global__ __launch_bounds__(kBlock) void sde_squash_forward_kernel(SdeArgs a, const float* __restrict__ mean,
+                                                                   const float* __restrict__ lat, size_t stride,
+                                                                   const float* __restrict__ std, float* __restrict__ act,
+                                                                   float* __restrict__ act_env, float* __restrict__ logp,
+                                                                   float* __restrict__ gauss, float* __restrict__ var_out) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int l = lane_id();
+  const int64_t e = (int64_t)blockIdx.x * kWaves + wave;
+  if (e >= a.n) return;                                 // wave-uniform
+  float noise[A], var[A];
+  sde_row_sums<A>(a, l, a.gid0 + (uint64_t)e, lat + (size_t)e * stride, std, noise, var);
+  if (l != 0) return;
+  float lp = 0.0f;
+#pragma unroll
+  for (int k = 0; k < A; ++k) {
+    const float m = mean[(size_t)e * A + k];
+    const float u = sde_action(m, noise[k]);
+    float t, om;
+    sde_squash(u, t, om);
+    act[(size_t)e * A + k] = t;
+    act_env[(size_t)e * A + k] = sde_unscale(t, a.low[k], a.high[k]);
+    if (gauss) {
+      gauss[(size_t)e * A + k] = u;
+      var_out[(size_t)e * A + k] = var[k];
+    }
+    lp = lp + sde_squash_logp_term(u, m, var[k], om);
+  }
+  logp[e] = lp;
+}
+
+// The squashed head's backward.  A wave owns partial p of g_std: rows [p R, min(n, (p + 1) R)), R =
+// sde_rows_per_partial(n).  Pass-outer, row-inner: within a pass of 256 latents a lane keeps the 4 A std values
+// and 4 A g_std accumulators of its elements in registers at any L, walks the partial's rows in ascending order,
+// rebuilds each row's normals as the forward did, stores its four g_lat values with one 16-B store and adds its
+// terms of g_std; then it stores the 4 A partial sums to scratch [P][L][A].  The price: the row tail (G, gn, gv:
+// two exp, a tanh, a few divisions, wave-uniform) is recomputed in every pass.  Lane 0 stores g_mean in its
+// first pass.  No lane waits for another; a lane at or past L stores nothing.
+template <int A>
+__global__ __launch_bounds__(kBlock) void sde_squash_backward_kernel(
+    SdeArgs a, int R, const float* __restrict__ mean, const float* __restrict__ lat, size_t stride,
+    const float* __restrict__ std, const float* __restrict__ gauss, const float* __restrict__ var,
+    const float* __restrict__ g_act, const float* __restrict__ g_logp, float* __restrict__ g_mean,
+    float* __restrict__ g_lat, size_t g_stride, float* __restrict__ part) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int l = lane_id();
+  const int64_t p = (int64_t)blockIdx.x * kWaves + wave;
+  const int64_t e0 = p * R;
+  if (e0 >= a.n) return;                                // wave-uniform
+  const int64_t e1 = e0 + R < a.n ? e0 + R : a.n;
+  for (int j0 = kSdePerLane * l; j0 < a.L; j0 += kSdePass) {
+    float s[4 * A], gs[4 * A];
+#pragma unroll
+    for (int i = 0; i < 4 * A; ++i) {
+      s[i] = std[(size_t)j0 * A + i];
+      gs[i] = 0.0f;
+    }
+    for (int64_t e = e0; e < e1; ++e) {
+      const float gl = g_logp ? g_logp[e] : 0.0f;
+      float gn[A], gv[A];
+#pragma unroll
+      for (int k = 0; k < A; ++k) {
+        const size_t at = (size_t)e * A + k;
+        float G;
+        sde_squash_grad_tail(gauss[at], mean[at], var[at], g_act ? g_act[at] : 0.0f, gl, G, gn[k], gv[k]);
+        if (j0 == 0) g_mean[at] = G;                    // lane 0, first pass
+      }
+      const float4 lv = *reinterpret_cast<const float4*>(lat + (size_t)e * stride + j0);
+      const float x[4] = {lv.x, lv.y, lv.z, lv.w};
+      float gx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int m = 0; m < A; ++m) {
+        uint32_t o[4];
+        float z[4];
+        sde_block(a.seed, a.gid0 + (uint64_t)e, a.epoch, (uint32_t)(j0 / 4) * A + m, o);
+        sde_normals(o, z);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = 4 * m + q;
+          sde_grad_accum(x[i / A], s[i], z[q], gn[i % A], gv[i % A], gx[i / A], gs[i]);
+        }
+      }
+      *reinterpret_cast<float4*>(g_lat + (size_t)e * g_stride + j0) = make_float4(gx[0], gx[1], gx[2], gx[3]);
+    }
+    float* const dst = part + ((size_t)p * a.L + j0) * A;     // 16-B aligned: scratch is, and (p L + j0) A % 4 == 0
+#pragma unroll
+    for (int m = 0; m < A; ++m)
+      *reinterpret_cast<float4*>(dst + 4 * m) = make_float4(gs[4 * m], gs[4 * m + 1], gs[4 * m + 2], gs[4 * m + 3]);
+  }
+}
+
+// g_std [L][A] from the P partials (sde_partials_sum's order).  A block takes 16 elements: wave w, lane
+// 16 sl + ie is strand 4 w + sl of element ie; the strands of a wave meet by two lane exchanges, the waves in LDS.
+static_assert(kSdeStrands == 4 * kWaves, "sde_std_finalise_kernel's strands are 4 per wave");
+__global__ __launch_bounds__(kBlock) void sde_std_finalise_kernel(int P, int LA, const float* __restrict__ part,
+                                                                 float* __restrict__ g_std) {
+  __shared__ float sums[kWaves][16];
+  const int w = threadIdx.x / kWave, l = lane_id();
+  const int ie = l % 16, sl = l / 16;
+  const int i = blockIdx.x * 16 + ie;
+  float acc = 0.0f;
+  if (i < LA)
+    for (int p = 4 * w + sl; p < P; p += kSdeStrands) acc = acc + part[(size_t)p * LA + i];
+  acc = acc + __shfl_xor(acc, 16);
+  acc = acc + __shfl_xor(acc, 32);
+  if (sl == 0) sums[w][ie] = acc;
+  __syncthreads();
+  if (threadIdx.x < 16 && i < LA) g_std[i] = (sums[0][ie] + sums[1][ie]) + (sums[2][ie] + sums[3][ie]);
 }
 
 // blocks_per_env = L * A / 4; thread t of the grid owns block t % blocks_per_env of env t / blocks_per_env.

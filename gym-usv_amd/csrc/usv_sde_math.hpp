@@ -29,6 +29,28 @@
 // (+0.0f for a lane without latents) are added by a balanced binary tree over the lanes in lane order
 // (sde_tree_sum: neighbours first).  Float addition is commutative, so a butterfly in which every lane adds
 // its partner's value computes exactly this tree.
+//
+// The squashed, differentiable head (usv_sde_squash_forward / _backward: SAC's distribution, squash_output).
+// noise_k and var_k as above, then per action, every operation rounded on its own:
+//   u_k   = mean_k + noise_k                     the gaussian action (sde_action: bit-equal to the head above)
+//   a_k   = tanhf(u_k)
+//   t_k   = expf(-2 |u_k|);  q_k = 1 + t_k;  om_k = (4 t_k) / (q_k q_k)      1 - tanh^2 without a subtraction
+//   c_k   = om_k + 1e-6
+//   env_k = low_k + ((a_k + 1) * 0.5) * (high_k - low_k)
+//   logp  = sum_k (sde_logp_term(u_k, mean_k, var_k) - ln c_k),  k ascending from 0.0f
+// Two deviations from SB3: the log-probability is taken at u itself (SB3 goes through atanh(clamp(tanh(u))),
+// which only adds rounding), and 1 - tanh^2 is the exp form (1 - a a loses all its digits once a rounds to 1).
+// Backward, for upstream ga_k = dl/da_k and gl = dl/dlogp (sde_squash_grad_tail, wave-uniform per row):
+//   G_k  = ga_k om_k + gl (((2 a_k) om_k) / c_k)         = g_mean_k
+//   gn_k = G_k - (gl d_k) / s2_k                          the gradient of noise_k;  d_k = u_k - mean_k
+//   gv_k = gl ((d_k d_k) / ((2 s2_k) s2_k) - 0.5 / s2_k)  the gradient of var_k
+// and per matrix element (sde_grad_accum), two fused multiply-adds into each sum, in this order:
+//   g_lat_j  = fmaf(gn_k, std_jk z_jk, .) then fmaf(gv_k, (2 lat_j)(std_jk std_jk), .)    k ascending from +0.0f
+//   g_std_jk = fmaf(gn_k lat_j, z_jk, .)  then fmaf(gv_k, (2 (lat_j lat_j)) std_jk, .)    rows ascending
+// The sum over rows of g_std.  R = ceil(n / 1024) rows per partial, P = ceil(n / R) <= 1024 partials; partial p
+// adds rows [p R, min(n, (p + 1) R)) in ascending order from +0.0f.  The P partials of an element are added by
+// 16 strands, strand s taking p = s, s + 16, .. in ascending order from +0.0f, and the 16 strand sums by a
+// balanced binary tree in strand order, neighbours first (sde_partials_sum).
 #pragma once
 
 #include <math.h>
@@ -146,6 +168,85 @@ USV_SDE_HD float sde_logp_term(float a, float mean, float var) {
   const float t = q / den;
   const float lg = 0.5f * logf(s2);
   return (-t - lg) - kSdeHalfLn2Pi;
+}
+
+// ---- the squashed head
+constexpr int kSdeMaxPartials = 1024;              // partial sums of g_std over rows
+constexpr int kSdeStrands = 16;                    // strands that add the partials of one element
+
+USV_SDE_HD int64_t sde_rows_per_partial(int64_t n) { return (n + kSdeMaxPartials - 1) / kSdeMaxPartials; }
+USV_SDE_HD int64_t sde_partials(int64_t n) {
+  const int64_t R = sde_rows_per_partial(n);
+  return R > 0 ? (n + R - 1) / R : 0;
+}
+
+// a = tanh(u) and om = 1 - tanh(u)^2 = 4 t / (1 + t)^2 with t = exp(-2 |u|): no subtraction, no overflow.
+USV_SDE_HD void sde_squash(float u, float& a, float& om) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  a = tanhf(u);
+  const float t = expf(-2.0f * fabsf(u));
+  const float q = 1.0f + t;
+  om = (4.0f * t) / (q * q);
+}
+
+// SB3's unscale_action: [-1, 1] to the Box.
+USV_SDE_HD float sde_unscale(float a, float low, float high) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return low + ((a + 1.0f) * 0.5f) * (high - low);
+}
+
+// One action's term of the squashed log-probability: the Gaussian term at u minus ln(1 - tanh^2 + eps).
+USV_SDE_HD float sde_squash_logp_term(float u, float mean, float var, float om) {
+  return sde_logp_term(u, mean, var) - logf(om + kSdeEps);
+}
+
+// One action's row gradients from the saved u and var: G (= g_mean), gn (of noise_k), gv (of var_k).
+USV_SDE_HD void sde_squash_grad_tail(float u, float mean, float var, float ga, float gl, float& G, float& gn,
+                                     float& gv) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float a, om;
+  sde_squash(u, a, om);
+  const float c = om + kSdeEps;
+  const float s2 = var + kSdeEps;
+  const float d = u - mean;
+  const float lg = ((2.0f * a) * om) / c;
+  G = ga * om + gl * lg;
+  gn = G - (gl * d) / s2;
+  gv = gl * ((d * d) / ((2.0f * s2) * s2) - 0.5f / s2);
+}
+
+// One matrix element's terms of g_lat_j and g_std_jk.
+USV_SDE_HD void sde_grad_accum(float lat, float std, float z, float gn, float gv, float& g_lat, float& g_std) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float w = sde_weight(std, z);
+  const float vl = (2.0f * lat) * (std * std);
+  const float nl = gn * lat;
+  const float vs = (2.0f * (lat * lat)) * std;
+  g_lat = fmaf(gn, w, g_lat);
+  g_lat = fmaf(gv, vl, g_lat);
+  g_std = fmaf(nl, z, g_std);
+  g_std = fmaf(gv, vs, g_std);
+}
+
+// The P partials of one element (part[p * stride]) by strands and tree.
+USV_SDE_HD float sde_partials_sum(const float* part, size_t stride, int P) {
+  float s[kSdeStrands];
+  for (int t = 0; t < kSdeStrands; ++t) {
+    float acc = 0.0f;
+    for (int p = t; p < P; p += kSdeStrands) acc = acc + part[(size_t)p * stride];
+    s[t] = acc;
+  }
+  for (int h = 1; h < kSdeStrands; h *= 2)
+    for (int i = 0; i < kSdeStrands; i += 2 * h) s[i] = s[i] + s[i + h];
+  return s[0];
 }
 
 }  // namespace usv

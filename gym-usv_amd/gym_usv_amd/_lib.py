@@ -103,7 +103,8 @@ class UsvRolloutFrames(ctypes.Structure):
 
 
 class UsvSde(ctypes.Structure):
-    """usv_sde: shape, generator key and Box bounds of the fused gSDE head (usv_sde_sample / usv_sde_weights)."""
+    """usv_sde: shape, generator key and Box bounds of the fused gSDE head (usv_sde_sample / usv_sde_weights /
+    usv_sde_squash_forward / _backward)."""
     _fields_ = [("n", ctypes.c_int32), ("latent_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("gid0", ctypes.c_uint64),
                 ("low", ctypes.c_float * 4), ("high", ctypes.c_float * 4)]
@@ -172,6 +173,11 @@ SIGNATURES = [
                                           _vp, _vp, _vp, _vp, _vp, _vp]),
     ("usv_sde_sample", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     ("usv_sde_weights", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _vp]),
+    ("usv_sde_squash_forward", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp]),
+    ("usv_sde_squash_scratch_floats", _sz, [ctypes.POINTER(UsvSde)]),
+    ("usv_sde_squash_backward", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _sz, _vp, _vp, _vp]),
     ("usv_replay_put_obs", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _sz, _vp, _vp]),
     ("usv_replay_put_step", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("usv_replay_gather", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -20,18 +20,58 @@ launch that uses it.  ``reset_noise`` only increments ``epoch``.  ``weights(std)
 inspection, tests and checkpoints; a one-hot latent row makes ``sample`` return a row of it bit for bit.
 
 The arithmetic is float32 in the order gym-usv_amd/csrc/usv_sde_math.hpp fixes; tests/sde_ref.py restates
-it in float64.  The update-time ``log_prob`` and its gradient stay torch autograd: they never needed W.
+it in float64.  PPO's update-time ``log_prob`` and its gradient stay torch autograd: they never needed W.
+
+SAC differentiates through the sample, so ``DeviceSDE.squashed`` is the same head with ``squash_output=True``
+and a HIP backward (``usv_sde_squash_forward`` / ``_backward``): the backward rebuilds the normals from the
+same counters, so nothing of size [B, L, A] is saved between the two.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import ptr as _ptr
 
 MAX_LATENT = 4096
+
+SquashedSample = collections.namedtuple("SquashedSample", "actions env_actions log_prob gaussian_actions")
+
+
+class _Squashed(torch.autograd.Function):
+    """``DeviceSDE.squashed`` under autograd: the forward writes fresh tensors (the saved ``gauss`` / ``var`` must
+    outlive the head's next call), the backward is ``usv_sde_squash_backward`` with the forward's epoch."""
+
+    @staticmethod
+    def forward(ctx, head, mean, latent, std):
+        n, A = head.n, head.act_dim
+        f4 = dict(dtype=torch.float32, device=head.device)
+        act, env, gauss, var = (torch.empty((n, A), **f4) for _ in range(4))
+        logp = torch.empty((n,), **f4)
+        head._squash_forward(mean, latent, std, (act, env, logp, gauss, var))
+        ctx.head, ctx.epoch = head, head._epoch
+        ctx.save_for_backward(mean, latent, std, gauss, var)
+        ctx.mark_non_differentiable(env, gauss)
+        ctx.set_materialize_grads(False)                    # an unused output's gradient stays None: NULL, zeros
+        return act, env, logp, gauss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_act, g_env, g_logp, g_gauss):
+        head = ctx.head
+        mean, latent, std, gauss, var = ctx.saved_tensors
+        n, L, A = head.n, head.latent_dim, head.act_dim
+        f4 = dict(dtype=torch.float32, device=head.device)
+        g_act = None if g_act is None else g_act.contiguous()
+        g_logp = None if g_logp is None else g_logp.contiguous()
+        g_mean, g_lat, g_std = torch.empty((n, A), **f4), torch.empty((n, L), **f4), torch.empty((L, A), **f4)
+        head._squash_backward(ctx.epoch, mean, latent, std, gauss, var, g_act, g_logp, g_mean, g_lat, g_std)
+        need = ctx.needs_input_grad
+        return None, g_mean if need[1] else None, g_lat if need[2] else None, g_std if need[3] else None
 
 
 class DeviceSDE:
@@ -77,6 +117,7 @@ class DeviceSDE:
         self._sp = ctypes.byref(self._s)
         f4 = dict(dtype=torch.float32, device=device)
         self._out = (torch.zeros((n, A), **f4), torch.zeros((n, A), **f4), torch.zeros((n,), **f4))
+        self._sq_out = self._scratch = None                # squashed's buffers, made by its first call
 
     @property
     def epoch(self):
@@ -128,3 +169,65 @@ class DeviceSDE:
         _lib.check(self.lib.usv_sde_weights(self._sp, self._epoch, _ptr(std), _ptr(out),
                                             _lib.stream_ptr(self.device)), self.lib)
         return out
+
+    def _latent_stride(self, name, t):
+        return _lib.check_rows(name, t, torch.float32, (self.n, self.latent_dim), self.device, stride_multiple=4,
+                               align=16)
+
+    def _squash_forward(self, mean, latent, std, out):
+        n, L, A = self.n, self.latent_dim, self.act_dim
+        _lib.check_tensor("mean", mean, torch.float32, (n, A), self.device)
+        _lib.check_tensor("std", std, torch.float32, (L, A), self.device)
+        stride = self._latent_stride("latent", latent)
+        act, env, logp, gauss, var = out
+        _lib.check(self.lib.usv_sde_squash_forward(self._sp, self._epoch, _ptr(mean), _ptr(latent), stride, _ptr(std),
+                                                   _ptr(act), _ptr(env), _ptr(logp), _ptr(gauss), _ptr(var),
+                                                   _lib.stream_ptr(self.device)), self.lib)
+
+    def _squash_backward(self, epoch, mean, latent, std, gauss, var, g_act, g_logp, g_mean, g_lat, g_std):
+        n, L, A = self.n, self.latent_dim, self.act_dim
+        for name, t, shape in (("g_act", g_act, (n, A)), ("g_logp", g_logp, (n,)), ("g_mean", g_mean, (n, A)),
+                               ("g_std", g_std, (L, A)), ("gauss", gauss, (n, A)), ("var", var, (n, A))):
+            if t is not None:
+                _lib.check_tensor(name, t, torch.float32, shape, self.device)
+        if self._scratch is None:
+            self._scratch = torch.empty((self.lib.usv_sde_squash_scratch_floats(self._sp),), dtype=torch.float32,
+                                        device=self.device)
+        _lib.check(self.lib.usv_sde_squash_backward(
+            self._sp, epoch, _ptr(mean), _ptr(latent), self._latent_stride("latent", latent), _ptr(std), _ptr(gauss),
+            _ptr(var), _ptr(g_act), _ptr(g_logp), _ptr(g_mean), _ptr(g_lat), self._latent_stride("g_lat", g_lat),
+            _ptr(g_std), _ptr(self._scratch), _lib.stream_ptr(self.device)), self.lib)
+
+    def squashed(self, mean, latent, std):
+        """SAC's head (``squash_output=True``, ``learn_features=True``): ``SquashedSample(actions, env_actions,
+        log_prob, gaussian_actions)`` with ``gaussian_actions = mean + latent @ W`` [N, A] (bit-equal to
+        ``sample``'s unclipped action), ``actions = tanh(gaussian_actions)``, ``env_actions = low + (actions + 1)
+        * 0.5 * (high - low)`` (SB3's ``unscale_action``) and ``log_prob`` [N] = the Gaussian log-probability of
+        ``gaussian_actions`` minus ``sum(ln(1 - actions^2 + 1e-6))``, with ``1 - actions^2`` computed as
+        ``4 t / (1 + t)^2``, ``t = exp(-2 |u|)``.  Arguments as ``sample``'s.
+
+        No input requires grad, or under ``torch.no_grad()``: one launch into this object's persistent buffers
+        (``copy`` as for ``sample``).  Otherwise the call is a ``torch.autograd.Function``: the forward writes
+        fresh tensors, and ``backward`` (once differentiable; two launches on the current stream) returns the
+        gradients of ``actions`` and ``log_prob`` with respect to ``mean``, ``latent`` (through the noise and
+        the variance) and ``std`` (chain ``log_std.exp()`` in front and autograd carries it into ``log_std``).
+        ``env_actions`` and ``gaussian_actions`` carry no gradient.  The epoch is the forward's: a
+        ``reset_noise()`` before ``backward()`` does not change the backward's matrix.  The backward's scratch
+        belongs to the head: backward calls of one head must be stream-ordered.
+
+        How SAC uses it.  One head of ``num_envs`` rows collects: rows are global env ids, and
+        ``reset_noise()`` every ``sde_sample_freq`` steps.  A second head of ``batch_size`` rows, with another
+        seed, serves the update: row = position in the minibatch, ``reset_noise()`` once per gradient step as
+        ``SAC.train`` does, so the observations (with grad) and the next observations (without) of that step
+        see the same matrices."""
+        if torch.is_grad_enabled() and (mean.requires_grad or latent.requires_grad or std.requires_grad):
+            return SquashedSample(*_Squashed.apply(self, mean, latent, std))
+        if self._sq_out is None:
+            n, A = self.n, self.act_dim
+            f4 = dict(dtype=torch.float32, device=self.device)
+            self._sq_out = tuple(torch.zeros(s, **f4) for s in ((n, A), (n, A), (n,), (n, A), (n, A)))
+        self._squash_forward(mean.detach(), latent.detach(), std.detach(), self._sq_out)
+        act, env, logp, gauss, _ = self._sq_out
+        if self.copy:
+            return SquashedSample(act.clone(), env.clone(), logp.clone(), gauss.clone())
+        return SquashedSample(act, env, logp, gauss)

@@ -551,6 +551,48 @@ int usv_sde_sample(const usv_sde* s, uint32_t epoch, const float* mean_dev, cons
                    float* logp_dev, void* stream);
 int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std_dev, float* w_dev, void* stream);
 
+/* The squashed, differentiable head: SAC's StateDependentNoiseDistribution(squash_output=True,
+ * learn_features=True) with its backward.  The same usv_sde (reserved = 0), the same matrix and the same
+ * noise_k and var_k as usv_sde_sample; additive (ABI v5 addition).  No host sync.
+ *
+ * usv_sde_squash_forward(s, epoch, mean, lat, row stride, std, act [n][A], act_env [n][A], logp [n],
+ * gauss [n][A] or NULL, var [n][A] or NULL), one launch:
+ *   gauss_k = mean_k + noise_k                            <- sample: mean + get_noise (bit-equal to
+ *                                                            usv_sde_sample's act)
+ *   act_k   = tanh(gauss_k)                               <- TanhBijector.forward (actions_from_params)
+ *   om_k    = 4 t / (1 + t)^2, t = exp(-2 |gauss_k|)      <- 1 - tanh^2 of TanhBijector.log_prob_correction,
+ *                                                            without its subtraction
+ *   act_env_k = low_k + ((act_k + 1) * 0.5) * (high_k - low_k)   <- policy.unscale_action
+ *   logp    = sum_k (-(gauss_k - mean_k)^2 / (2 s2_k) - 0.5 ln s2_k - 0.5 ln 2 pi - ln(om_k + 1e-6))
+ *                                                         <- log_prob: the Gaussian term at gauss itself (SB3
+ *                                                            takes it at atanh(clamp(act))) minus the correction
+ *   var_k                                                 <- proba_distribution: mm(latent_sde ** 2, std ** 2)
+ * gauss and var are what the backward needs of the forward; NULL together on a call that is not differentiated.
+ *
+ * usv_sde_squash_backward(s, epoch, mean, lat, row stride, std, gauss, var, g_act [n][A] or NULL, g_logp [n] or
+ * NULL (NULL: zeros), g_mean [n][A], g_lat rows of latent_dim floats, its row stride, g_std [latent_dim][A],
+ * scratch), two launches on the stream, replaces autograd through sample_weights' rsample, get_noise's bmm,
+ * proba_distribution's mm and log_prob: the gradients of sum(g_act act) + sum(g_logp logp) with respect to
+ * mean, lat (through the noise and the variance: learn_features) and std (through the matrix std z and the
+ * variance), with the normals rebuilt from (seed, gid, epoch, element) as the forward built them.  Floats past
+ * latent_dim in a strided g_lat row are not written.  g_std's sum over rows has no atomics and a fixed order
+ * (csrc/usv_sde_math.hpp): partials of ceil(n / 1024) rows each in scratch, which holds
+ * usv_sde_squash_scratch_floats(s) = P * latent_dim * act_dim floats (0 for a usv_sde that would be refused),
+ * then one sum per element.  Two backward calls that share a scratch must be stream-ordered.
+ *
+ * USV_ERR_ARG, before any HIP call, for everything usv_sde_sample refuses, and: exactly one of gauss / var
+ * NULL (forward); a NULL gauss, var or scratch, a g_lat or scratch that is not 16-B aligned, a g_lat row
+ * stride below latent_dim or not a multiple of 4 (backward).  Then the device-memory checks. */
+int usv_sde_squash_forward(const usv_sde* s, uint32_t epoch, const float* mean_dev, const float* lat_dev,
+                           size_t lat_row_stride_floats, const float* std_dev, float* act_dev, float* act_env_dev,
+                           float* logp_dev, float* gauss_dev, float* var_dev, void* stream);
+size_t usv_sde_squash_scratch_floats(const usv_sde* s);
+int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean_dev, const float* lat_dev,
+                            size_t lat_row_stride_floats, const float* std_dev, const float* gauss_dev,
+                            const float* var_dev, const float* g_act_dev, const float* g_logp_dev, float* g_mean_dev,
+                            float* g_lat_dev, size_t g_lat_row_stride_floats, float* g_std_dev, float* scratch_dev,
+                            void* stream);
+
 /* Device replay buffer: SB3's ReplayBuffer (common/buffers.py: add, sample, _get_samples with
  * optimize_memory_usage=False and handle_timeout_termination=True) and the terminal-observation
  * substitution of OffPolicyAlgorithm._store_transition, for windows of k frames of d floats that evolve by
