@@ -35,6 +35,13 @@ this image, so this is a compact PPO with the same hyper-parameters where they c
   ``Normal.log_prob``.  ``reset_noise`` is then a host integer.  The update is unchanged: it only ever
   needed the variance.  The noise differs from torch's generator, so runs with and without the flag are
   two samples of the same algorithm, not the same numbers.
+* ``--eval-kernel`` (with ``--sde-kernel``; ``train(..., eval_kernel=True)``): the update's head is
+  ``DeviceSDE.evaluate``: the log-probability of the stored actions, the ratio and the clipped surrogate in one
+  HIP launch and their gradients in two, in place of the torch ops of ``ActorCritic.dist``, ``log_prob``, ``exp``,
+  ``clamp`` and ``min`` and their autograd.  Advantage normalisation, the value loss and ``-logp.mean()`` stay
+  torch.  ``--check-eval`` (a test mode) evaluates both heads on every minibatch and records
+  ``eval_logp_diff_max``, the largest ``|logp_kernel - logp_torch| / (1 + sum_k (d^2 / s2 + |ln s2|))`` of the
+  update, read back once per update.
 
 Rollout size at 4096 envs.  config_ppo's ``n_steps=2048, batch_size=64`` are for the reference's 4
 envs: 8 192 samples per update in 128 minibatches.  With 4096 envs the same n_steps would put 8.4 M
@@ -114,7 +121,8 @@ class ActorCritic(nn.Module):
 class PPO:
     """Rollout + update over a ``UsvVectorEnv`` (any registered id with a Box action space)."""
 
-    def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, frames=False, sde_kernel=False, **cfg):
+    def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, frames=False, sde_kernel=False,
+                 eval_kernel=False, check_eval=False, **cfg):
         from gym_usv_amd.sb3 import DeviceFrameStack
         self.cfg = dict(CONFIG_PPO, **cfg)
         self.env, self.n_steps, self.batch_size = env, n_steps, batch_size
@@ -127,6 +135,10 @@ class PPO:
         self.frames = frames
         if sde_kernel and not (fused and self.cfg["use_sde"]):
             raise ValueError("sde_kernel=True needs fused=True and use_sde=True")
+        if (eval_kernel or check_eval) and not (fused and sde_kernel):
+            raise ValueError("eval_kernel=True and check_eval=True need fused=True and sde_kernel=True")
+        self.eval_kernel, self.check_eval = eval_kernel, check_eval
+        self._eval_diff = None                          # check_eval: the update's largest normalised |dlogp|
         self.head = None
         if not fused:
             self.stack = DeviceFrameStack(self.N, D, self.cfg["n_stack"], self.device)
@@ -261,6 +273,45 @@ class PPO:
             adv[t] = gae
         return adv, adv + self.b_val
 
+    def policy_terms(self, obs, actions, old_logp, a_):
+        """(log_prob [B], policy loss, the torch distribution or None) of one minibatch.  ``eval_kernel``: the
+        three come from ``DeviceSDE.evaluate`` on the policy's mean and detached latent; ``check_eval``: both heads
+        run and the largest normalised difference of their log-probabilities is kept on the device."""
+        clip = self.cfg["clip"]
+        if not (self.eval_kernel or self.check_eval):
+            dist, _ = self.model.dist(obs)
+            logp = dist.log_prob(actions).sum(-1)
+            ratio = (logp - old_logp).exp()
+            return logp, -torch.min(ratio * a_, ratio.clamp(1 - clip, 1 + clip) * a_).mean(), dist
+        lat = self.model.pi_body(obs)
+        mean, std = self.model.mu(lat), self.model.log_std.exp()
+        lat = lat.detach()
+        if self.eval_kernel:
+            ev = self.head.evaluate(mean, lat, std, actions, old_logp, a_, clip)
+            logp, pg = ev.log_prob, -ev.surrogate.mean()
+        if self.check_eval or not self.eval_kernel:
+            s2 = (lat * lat) @ (std ** 2) + SDE_EPS
+            t_logp = torch.distributions.Normal(mean, torch.sqrt(s2), validate_args=False).log_prob(actions).sum(-1)
+        if not self.eval_kernel:
+            ratio = (t_logp - old_logp).exp()
+            logp, pg = t_logp, -torch.min(ratio * a_, ratio.clamp(1 - clip, 1 + clip) * a_).mean()
+        if self.check_eval:
+            with torch.no_grad():
+                k_logp = logp if self.eval_kernel else self.head.evaluate(mean, lat, std, actions).log_prob
+                d = actions - mean
+                scale = 1.0 + (d * d / s2 + s2.log().abs()).sum(-1)
+                worst = ((k_logp - t_logp).abs() / scale).max()
+                self._eval_diff = worst if self._eval_diff is None else torch.maximum(self._eval_diff, worst)
+        return logp, pg, None
+
+    def update_record(self, stats):
+        s = torch.stack(stats).mean(0).tolist()
+        rec = {"policy_loss": s[0], "value_loss": s[1], "entropy": s[2],
+               "std_mean": float(self.model.log_std.detach().exp().mean())}
+        if self.check_eval:
+            rec["eval_logp_diff_max"], self._eval_diff = float(self._eval_diff), None
+        return rec
+
     def update(self):
         c = self.cfg
         adv, ret = self.advantages()
@@ -277,10 +328,7 @@ class PPO:
                 i = perm[k:k + self.batch_size]
                 a_ = adv[i]
                 a_ = (a_ - a_.mean()) / (a_.std() + 1e-8)
-                dist, _ = self.model.dist(obs[i])
-                logp = dist.log_prob(act[i]).sum(-1)
-                ratio = (logp - logp0[i]).exp()
-                pg = -torch.min(ratio * a_, ratio.clamp(1 - c["clip"], 1 + c["clip"]) * a_).mean()
+                logp, pg, dist = self.policy_terms(obs[i], act[i], logp0[i], a_)
                 vl = ((self.model.value(obs[i]) - ret[i]) ** 2).mean()
                 ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
                 loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
@@ -289,9 +337,7 @@ class PPO:
                 nn.utils.clip_grad_norm_(self.model.parameters(), c["max_grad_norm"])
                 self.opt.step()
                 stats.append(torch.stack((pg.detach(), vl.detach(), ent.detach())))
-        s = torch.stack(stats).mean(0).tolist()
-        return {"policy_loss": s[0], "value_loss": s[1], "entropy": s[2],
-                "std_mean": float(self.model.log_std.detach().exp().mean())}
+        return self.update_record(stats)
 
     def update_frames(self, M):
         """``update``'s loop with every minibatch read by ``DeviceRollout.gather`` (frame storage has no
@@ -304,10 +350,7 @@ class PPO:
                 mb = self.ro.gather(perm[k:k + self.batch_size])
                 a_ = mb.advantages
                 a_ = (a_ - a_.mean()) / (a_.std() + 1e-8)
-                dist, _ = self.model.dist(mb.observations)
-                logp = dist.log_prob(mb.actions).sum(-1)
-                ratio = (logp - mb.old_log_prob).exp()
-                pg = -torch.min(ratio * a_, ratio.clamp(1 - c["clip"], 1 + c["clip"]) * a_).mean()
+                logp, pg, dist = self.policy_terms(mb.observations, mb.actions, mb.old_log_prob, a_)
                 vl = ((self.model.value(mb.observations) - mb.returns) ** 2).mean()
                 ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
                 loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
@@ -316,9 +359,7 @@ class PPO:
                 nn.utils.clip_grad_norm_(self.model.parameters(), c["max_grad_norm"])
                 self.opt.step()
                 stats.append(torch.stack((pg.detach(), vl.detach(), ent.detach())))
-        s = torch.stack(stats).mean(0).tolist()
-        return {"policy_loss": s[0], "value_loss": s[1], "entropy": s[2],
-                "std_mean": float(self.model.log_std.detach().exp().mean())}
+        return self.update_record(stats)
 
     def episode_stats(self):
         out = {"mean_abs_ye": float(torch.stack(self.abs_ye).mean())} if self.abs_ye else {}
@@ -340,11 +381,11 @@ class PPO:
 
 
 def train(env_id="usv-simple", envs=4096, updates=10, n_steps=32, batch_size=4096, seed=0, log=print, fused=False,
-          frames=False, sde_kernel=False, **cfg):
+          frames=False, sde_kernel=False, eval_kernel=False, check_eval=False, **cfg):
     import gym_usv_amd
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False)   # each step is consumed at once
     ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, frames=frames,
-              sde_kernel=sde_kernel, **cfg)
+              sde_kernel=sde_kernel, eval_kernel=eval_kernel, check_eval=check_eval, **cfg)
     hist = []
     t0 = time.perf_counter()
     for u in range(updates):
@@ -372,12 +413,18 @@ def main():
                     help="with --fused: one frame per step in the rollout, minibatches by DeviceRollout.gather")
     ap.add_argument("--sde-kernel", action="store_true",
                     help="with --fused and gSDE: the rollout's action head is one DeviceSDE launch per step")
+    ap.add_argument("--eval-kernel", action="store_true",
+                    help="with --sde-kernel: the update's log_prob, ratio and clipped surrogate are DeviceSDE.evaluate")
+    ap.add_argument("--check-eval", action="store_true",
+                    help="with --sde-kernel: evaluate both heads on every minibatch and record eval_logp_diff_max")
     ap.add_argument("--log", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     if a.frames and not a.fused:
         ap.error("--frames needs --fused")
     if a.sde_kernel and (not a.fused or a.no_sde):
         ap.error("--sde-kernel needs --fused and gSDE (no --no-sde)")
+    if (a.eval_kernel or a.check_eval) and not a.sde_kernel:
+        ap.error("--eval-kernel and --check-eval need --sde-kernel")
     f = open(a.log, "a") if a.log else None
 
     def log(s):
@@ -388,9 +435,10 @@ def main():
     if f:
         log(json.dumps({"config": {**CONFIG_PPO, "use_sde": not a.no_sde, "env_id": a.env_id, "envs": a.envs,
                                    "n_steps": a.n_steps, "batch_size": a.batch_size, "seed": a.seed,
-                                   "fused": a.fused, "frames": a.frames, "sde_kernel": a.sde_kernel}}))
+                                   "fused": a.fused, "frames": a.frames, "sde_kernel": a.sde_kernel,
+                                   "eval_kernel": a.eval_kernel, "check_eval": a.check_eval}}))
     train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, fused=a.fused, frames=a.frames,
-          sde_kernel=a.sde_kernel, use_sde=not a.no_sde)
+          sde_kernel=a.sde_kernel, eval_kernel=a.eval_kernel, check_eval=a.check_eval, use_sde=not a.no_sde)
 
 
 if __name__ == "__main__":

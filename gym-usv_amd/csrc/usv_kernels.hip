@@ -24,7 +24,8 @@
 //   usv_rollout_frames_math.hpp  frame-deduplicated obs storage: rows, live mask, clear rule (host C++, no HIP)
 //   usv_rollout_frames.hpp  frame store and minibatch gather (usv_rollout_put_obs_frames / usv_rollout_gather)
 //   usv_sde_math.hpp      gSDE head: Philox numbering, Box-Muller, sums, clip, log-probability (host C++, no HIP)
-//   usv_sde.hpp           fused gSDE action head (usv_sde_sample / usv_sde_weights / usv_sde_squash_forward / _backward)
+//   usv_sde.hpp           fused gSDE action head (usv_sde_sample / usv_sde_weights / usv_sde_squash_forward / _backward /
+//                         usv_sde_eval_forward / _backward)
 //   usv_replay_math.hpp   replay buffer: slots, frame rows, age and live masks (host C++, no HIP)
 //   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
@@ -1349,6 +1350,84 @@ int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean,
   else
     hipLaunchKernelGGL(sde_squash_backward_kernel<2>, grid, block, 0, (hipStream_t)stream, a, R, mean, lat, stride, std,
                        gauss, var, g_act, g_logp, g_mean, g_lat, g_stride, scratch);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(sde_std_finalise_kernel, dim3((unsigned)((LA + 15) / 16)), block, 0, (hipStream_t)stream, P, LA,
+                     scratch, g_std);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// The checks of usv_sde_eval_* that need no HIP call: the struct's shape (its n, key and bounds are not the
+// evaluation's) and the call's row count.
+static int sde_eval_check(const usv_sde* s, int32_t rows) {
+  if (!s) return fail(USV_ERR_ARG, "null usv_sde");
+  if (s->act_dim != 1 && s->act_dim != 2) return fail(USV_ERR_ARG, "usv_sde: act_dim must be 1 or 2");
+  if (!sde_latent_ok(s->latent_dim))
+    return fail(USV_ERR_ARG, "usv_sde: latent_dim must be a multiple of 4 in [4, 4096]");
+  if (s->reserved != 0) return fail(USV_ERR_ARG, "usv_sde: reserved must be 0");
+  if (rows <= 0) return fail(USV_ERR_ARG, "usv_sde_eval: rows must be > 0");
+  return USV_OK;
+}
+
+int usv_sde_eval_forward(const usv_sde* s, int32_t rows, const float* mean, const float* lat, size_t stride,
+                         const float* std, const float* act, const float* old_logp, const float* adv, float clip,
+                         float* logp, float* sur, float* ratio, float* var, void* stream) {
+  int dev;
+  if (int rc = sde_eval_check(s, rows)) return rc;
+  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
+    return fail(USV_ERR_ARG, "usv_sde_eval_forward: the row stride must be a multiple of 4 and >= latent_dim");
+  const bool ppo = old_logp != nullptr;
+  if ((adv != nullptr) != ppo || (sur != nullptr) != ppo || (ratio != nullptr) != ppo)
+    return fail(USV_ERR_ARG, "usv_sde_eval_forward: old_logp, adv, sur and ratio must be all NULL or all set");
+  if (ppo && !(clip >= 0.0f)) return fail(USV_ERR_ARG, "usv_sde_eval_forward: clip must be >= 0 (and not NaN)");
+  const Buf all[] = {{lat, 16},          {mean, 4},     {std, 4},      {act, 4},        {logp, 4},
+                     {old_logp, 4, true}, {adv, 4, true}, {sur, 4, true}, {ratio, 4, true}, {var, 4, true}};
+  if (int rc = sde_bufs(all, 10, dev)) return rc;
+  DeviceGuard g(dev);
+  const dim3 grid((unsigned)(((int64_t)rows + kWaves - 1) / kWaves)), block(kBlock);
+  if (s->act_dim == 1)
+    hipLaunchKernelGGL(sde_eval_forward_kernel<1>, grid, block, 0, (hipStream_t)stream, (int)rows, s->latent_dim, mean, lat,
+                       stride, std, act, old_logp, adv, clip, logp, sur, ratio, var);
+  else
+    hipLaunchKernelGGL(sde_eval_forward_kernel<2>, grid, block, 0, (hipStream_t)stream, (int)rows, s->latent_dim, mean, lat,
+                       stride, std, act, old_logp, adv, clip, logp, sur, ratio, var);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+size_t usv_sde_eval_scratch_floats(const usv_sde* s, int32_t rows) {
+  if (sde_eval_check(s, rows)) return 0;
+  return (size_t)sde_partials(rows) * (size_t)s->latent_dim * (size_t)s->act_dim;
+}
+
+int usv_sde_eval_backward(const usv_sde* s, int32_t rows, const float* mean, const float* lat, size_t stride,
+                          const float* std, const float* act, const float* var, const float* ratio, const float* adv,
+                          float clip, const float* g_logp, const float* g_sur, float* g_mean, float* g_lat,
+                          size_t g_stride, float* g_std, float* scratch, void* stream) {
+  int dev;
+  if (int rc = sde_eval_check(s, rows)) return rc;
+  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
+    return fail(USV_ERR_ARG, "usv_sde_eval_backward: the row stride must be a multiple of 4 and >= latent_dim");
+  if (g_lat && (g_stride < (size_t)s->latent_dim || g_stride % 4 != 0))
+    return fail(USV_ERR_ARG, "usv_sde_eval_backward: the g_lat row stride must be a multiple of 4 and >= latent_dim");
+  if ((ratio != nullptr) != (adv != nullptr))
+    return fail(USV_ERR_ARG, "usv_sde_eval_backward: ratio and adv must be both NULL or both set");
+  if (g_sur && !ratio) return fail(USV_ERR_ARG, "usv_sde_eval_backward: g_sur needs ratio and adv");
+  if (ratio && !(clip >= 0.0f)) return fail(USV_ERR_ARG, "usv_sde_eval_backward: clip must be >= 0 (and not NaN)");
+  if (!scratch) return fail(USV_ERR_ARG, "usv_sde_eval_backward: null scratch");
+  const Buf all[] = {{lat, 16},       {g_lat, 16, true}, {scratch, 16},     {mean, 4},          {std, 4},
+                     {act, 4},        {var, 4},          {g_mean, 4},       {g_std, 4},         {ratio, 4, true},
+                     {adv, 4, true},  {g_logp, 4, true}, {g_sur, 4, true}};
+  if (int rc = sde_bufs(all, 13, dev)) return rc;
+  DeviceGuard g(dev);
+  const int R = (int)sde_rows_per_partial(rows), P = (int)sde_partials(rows), LA = s->latent_dim * s->act_dim;
+  const dim3 grid((unsigned)((P + kWaves - 1) / kWaves)), block(kBlock);
+  if (s->act_dim == 1)
+    hipLaunchKernelGGL(sde_eval_backward_kernel<1>, grid, block, 0, (hipStream_t)stream, (int)rows, s->latent_dim, R, mean,
+                       lat, stride, std, act, var, ratio, adv, clip, g_logp, g_sur, g_mean, g_lat, g_stride, scratch);
+  else
+    hipLaunchKernelGGL(sde_eval_backward_kernel<2>, grid, block, 0, (hipStream_t)stream, (int)rows, s->latent_dim, R, mean,
+                       lat, stride, std, act, var, ratio, adv, clip, g_logp, g_sur, g_mean, g_lat, g_stride, scratch);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(sde_std_finalise_kernel, dim3((unsigned)((LA + 15) / 16)), block, 0, (hipStream_t)stream, P, LA,
                      scratch, g_std);

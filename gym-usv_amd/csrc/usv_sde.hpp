@@ -13,6 +13,9 @@
 //   sde_squash_forward_kernel<A>, sde_squash_backward_kernel<A>, sde_std_finalise_kernel
 //                          SAC's squashed head (usv_sde_squash_forward / _backward): the same row sums with a
 //                          tanh tail, and its gradients with the normals rebuilt, not saved; see at each.
+//   sde_eval_forward_kernel<A>, sde_eval_backward_kernel<A>
+//                          PPO's evaluate_actions (usv_sde_eval_forward / _backward): the variance sums alone, the
+//                          log-probability of stored actions, the clipped surrogate, and their gradients.
 // The [L][A] std table is read once per wave, straight into registers: each element is used by one lane
 // of the wave, once, so staging it in LDS would add a write, a barrier and a read without saving a load;
 // the table (2 KiB at L = 256, A = 2) stays in L2 for the waves of the other envs.
@@ -255,6 +258,103 @@ __global__ __launch_bounds__(kBlock) void sde_weights_kernel(SdeArgs a, const fl
   float* const dst = w + (size_t)e * a.L * A + 4 * (size_t)b;
 #pragma unroll
   for (int q = 0; q < 4; ++q) dst[q] = sde_weight(std[4 * (size_t)b + q], z[q]);
+}
+
+// ---- PPO's evaluate_actions (usv_sde_eval_forward / _backward): stored actions under the current policy, no noise.
+// The forward: a wave per row.  sde_row_sums' latent and std loads without its Philox blocks (a copy for the same
+// reason as there), the A wave sums of var_k, then lane 0's tail: logp, and with old / adv the ratio and the clipped
+// surrogate.  var_out (the backward's saved var) is NULL on a call that will not be differentiated; old, adv, sur
+// and ratio are NULL together.
+template <int A>
+__global__ __launch_bounds__(kBlock) void sde_eval_forward_kernel(
+    int n, int L, const float* __restrict__ mean, const float* __restrict__ lat, size_t stride,
+    const float* __restrict__ std, const float* __restrict__ act, const float* __restrict__ old,
+    const float* __restrict__ adv, float clip, float* __restrict__ logp, float* __restrict__ sur,
+    float* __restrict__ ratio, float* __restrict__ var_out) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int l = lane_id();
+  const int64_t e = (int64_t)blockIdx.x * kWaves + wave;
+  if (e >= n) return;                                   // wave-uniform
+  const float* const row = lat + (size_t)e * stride;
+  float var[A];
+#pragma unroll
+  for (int k = 0; k < A; ++k) var[k] = 0.0f;
+  for (int j0 = kSdePerLane * l; j0 < L; j0 += kSdePass) {
+    const float4 lv = *reinterpret_cast<const float4*>(row + j0);     // row and stride are 16-B aligned
+    const float x[4] = {lv.x, lv.y, lv.z, lv.w};
+    float s[4 * A];
+#pragma unroll
+    for (int i = 0; i < 4 * A; ++i) s[i] = std[(size_t)j0 * A + i];
+#pragma unroll
+    for (int i = 0; i < 4 * A; ++i) sde_var_accum(x[i / A], s[i], var[i % A]);   // latent i / A, action i % A
+  }
+#pragma unroll
+  for (int k = 0; k < A; ++k) var[k] = sde_wave_sum(var[k]);
+  if (l != 0) return;
+  float lp = 0.0f;
+#pragma unroll
+  for (int k = 0; k < A; ++k) {
+    const size_t at = (size_t)e * A + k;
+    if (var_out) var_out[at] = var[k];
+    lp = lp + sde_logp_term(act[at], mean[at], var[k]);
+  }
+  logp[e] = lp;
+  if (old) {
+    float r;
+    sur[e] = sde_ppo_surrogate(lp, old[e], adv[e], clip, r);
+    ratio[e] = r;
+  }
+}
+
+// The backward: sde_squash_backward_kernel's shape without the normals.  A wave owns partial p of g_std, rows
+// [p R, min(n, (p + 1) R)); pass-outer, row-inner, the 4 A std values and g_std accumulators of a lane's elements in
+// registers.  The row tail (t, g_mean, gv: a few divisions, wave-uniform) is recomputed in every pass and lane 0
+// stores g_mean in its first.  ratio and adv are NULL together (no surrogate: t = gl); g_logp and g_sur may each be
+// NULL (zeros); g_lat is NULL where the latent needs no gradient, and then nothing of size [n][L] is written.
+template <int A>
+__global__ __launch_bounds__(kBlock) void sde_eval_backward_kernel(
+    int n, int L, int R, const float* __restrict__ mean, const float* __restrict__ lat, size_t stride,
+    const float* __restrict__ std, const float* __restrict__ act, const float* __restrict__ var,
+    const float* __restrict__ ratio, const float* __restrict__ adv, float clip, const float* __restrict__ g_logp,
+    const float* __restrict__ g_sur, float* __restrict__ g_mean, float* __restrict__ g_lat, size_t g_stride,
+    float* __restrict__ part) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int l = lane_id();
+  const int64_t p = (int64_t)blockIdx.x * kWaves + wave;
+  const int64_t e0 = p * R;
+  if (e0 >= n) return;                                  // wave-uniform
+  const int64_t e1 = e0 + R < n ? e0 + R : n;
+  for (int j0 = kSdePerLane * l; j0 < L; j0 += kSdePass) {
+    float s[4 * A], gs[4 * A];
+#pragma unroll
+    for (int i = 0; i < 4 * A; ++i) {
+      s[i] = std[(size_t)j0 * A + i];
+      gs[i] = 0.0f;
+    }
+    for (int64_t e = e0; e < e1; ++e) {
+      const float gl = g_logp ? g_logp[e] : 0.0f;
+      const float t = ratio ? sde_eval_row_grad(gl, g_sur ? g_sur[e] : 0.0f, ratio[e], adv[e], clip) : gl;
+      float gv[A];
+#pragma unroll
+      for (int k = 0; k < A; ++k) {
+        const size_t at = (size_t)e * A + k;
+        float G;
+        sde_eval_grad_tail(act[at], mean[at], var[at], t, G, gv[k]);
+        if (j0 == 0) g_mean[at] = G;                    // lane 0, first pass
+      }
+      const float4 lv = *reinterpret_cast<const float4*>(lat + (size_t)e * stride + j0);
+      const float x[4] = {lv.x, lv.y, lv.z, lv.w};
+      float gx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int i = 0; i < 4 * A; ++i) sde_eval_grad_accum(x[i / A], s[i], gv[i % A], gx[i / A], gs[i]);
+      if (g_lat)
+        *reinterpret_cast<float4*>(g_lat + (size_t)e * g_stride + j0) = make_float4(gx[0], gx[1], gx[2], gx[3]);
+    }
+    float* const dst = part + ((size_t)p * L + j0) * A;       // 16-B aligned: scratch is, and (p L + j0) A % 4 == 0
+#pragma unroll
+    for (int m = 0; m < A; ++m)
+      *reinterpret_cast<float4*>(dst + 4 * m) = make_float4(gs[4 * m], gs[4 * m + 1], gs[4 * m + 2], gs[4 * m + 3]);
+  }
 }
 
 }  // namespace usv

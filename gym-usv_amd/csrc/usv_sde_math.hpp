@@ -51,6 +51,20 @@
 // adds rows [p R, min(n, (p + 1) R)) in ascending order from +0.0f.  The P partials of an element are added by
 // 16 strands, strand s taking p = s, s + 16, .. in ascending order from +0.0f, and the 16 strand sums by a
 // balanced binary tree in strand order, neighbours first (sde_partials_sum).
+//
+// The evaluation head (usv_sde_eval_forward / _backward: PPO's evaluate_actions, no noise).  For stored actions
+// act_k, var_k as above (sde_var_accum: sample's terms, lanes and tree, so sample's bits), then
+//   logp  = sum_k sde_logp_term(act_k, mean_k, var_k),  k ascending from 0.0f
+// and, where old, adv and the clip range c are given (sde_ppo_surrogate),
+//   ratio = expf(logp - old);  rc = min(max(ratio, 1 - c), 1 + c);  s1 = ratio adv;  s2 = rc adv
+//   sur   = s2 < s1 ? s2 : s1
+// Backward, for upstream gl (of logp) and gs (of sur), from the saved var and ratio:
+//   t       = gl + (s1 <= s2 ? gs s1 : 0)                  torch.min / clamp under autograd, ties included
+//   s2v_k   = var_k + 1e-6;  d_k = act_k - mean_k
+//   g_mean_k = (t d_k) / s2v_k
+//   gv_k    = t ((d_k d_k) / ((2 s2v_k) s2v_k) - 0.5 / s2v_k)
+//   g_lat_j  = fmaf(gv_k, (2 lat_j)(std_jk std_jk), .)     k ascending from +0.0f
+//   g_std_jk = fmaf(gv_k, (2 (lat_j lat_j)) std_jk, .)     rows ascending, partials and their sum as above
 #pragma once
 
 #include <math.h>
@@ -247,6 +261,81 @@ USV_SDE_HD float sde_partials_sum(const float* part, size_t stride, int P) {
   for (int h = 1; h < kSdeStrands; h *= 2)
     for (int i = 0; i < kSdeStrands; i += 2 * h) s[i] = s[i] + s[i + h];
   return s[0];
+}
+
+// ---- the evaluation head (PPO's evaluate_actions, usv_sde_eval_forward / _backward)
+// One term of a lane's variance sum: sde_accum's second line, so var_k is sample's bit for bit.
+USV_SDE_HD void sde_var_accum(float lat, float std, float& var) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float l2 = lat * lat, s2 = std * std;
+  var = fmaf(l2, s2, var);
+}
+
+// torch.clamp(ratio, 1 - c, 1 + c): a NaN ratio stays NaN.
+USV_SDE_HD float sde_ppo_clamp(float ratio, float clip) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float lo = 1.0f - clip, hi = 1.0f + clip;
+  const float t = ratio < lo ? lo : ratio;
+  return t > hi ? hi : t;
+}
+
+// The two products of PPO's surrogate from the ratio: s1 = ratio adv, s2 = clamp(ratio) adv.
+USV_SDE_HD void sde_ppo_products(float ratio, float adv, float clip, float& s1, float& s2) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  s1 = ratio * adv;
+  s2 = sde_ppo_clamp(ratio, clip) * adv;
+}
+
+// ratio = exp(logp - old) and the clipped surrogate min(s1, s2) of one row.
+USV_SDE_HD float sde_ppo_surrogate(float logp, float old, float adv, float clip, float& ratio) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  ratio = expf(logp - old);
+  float s1, s2;
+  sde_ppo_products(ratio, adv, clip, s1, s2);
+  return s2 < s1 ? s2 : s1;
+}
+
+// The gradient of a row's logp for upstream gl (of logp) and gs (of the surrogate): torch.min and clamp under
+// autograd.  s1 is chosen where s1 <= s2 and d s1 / d logp = s1; an unclipped row ties (s1 == s2), min halves the
+// gradient between the two and clamp passes its half (bounds inclusive), which add to gs s1; a clipped row that
+// ties has adv = 0 = s1.
+USV_SDE_HD float sde_eval_row_grad(float gl, float gs, float ratio, float adv, float clip) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float s1, s2;
+  sde_ppo_products(ratio, adv, clip, s1, s2);
+  return gl + (s1 <= s2 ? gs * s1 : 0.0f);
+}
+
+// One action's gradients from the row's t (sde_eval_row_grad): g_mean_k and gv (of var_k; sde_squash_grad_tail's).
+USV_SDE_HD void sde_eval_grad_tail(float act, float mean, float var, float t, float& g_mean, float& gv) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float s2 = var + kSdeEps;
+  const float d = act - mean;
+  g_mean = (t * d) / s2;
+  gv = t * ((d * d) / ((2.0f * s2) * s2) - 0.5f / s2);
+}
+
+// One matrix element's terms of g_lat_j and g_std_jk: the variance half of sde_grad_accum.
+USV_SDE_HD void sde_eval_grad_accum(float lat, float std, float gv, float& g_lat, float& g_std) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float vl = (2.0f * lat) * (std * std);
+  const float vs = (2.0f * (lat * lat)) * std;
+  g_lat = fmaf(gv, vl, g_lat);
+  g_std = fmaf(gv, vs, g_std);
 }
 
 }  // namespace usv

@@ -15,7 +15,7 @@ The compute lives in libusvhip.so (HIP, gfx950) behind the C-ABI in include/usv_
 from ._lib import UsvLibError, load as load_library  # noqa: F401
 from .vector_env import ENV_SPECS, UsvVectorEnv  # noqa: F401
 from .rollout import DeviceRollout  # noqa: F401
-from .sde import DeviceSDE, SquashedSample  # noqa: F401
+from .sde import DeviceSDE, Evaluation, SquashedSample  # noqa: F401
 from .replay import DeviceReplay  # noqa: F401
 
 __all__ = ["make", "make_vec", "make_sb3_vec_env", "registry", "UsvVectorEnv", "UsvLibError", "ENV_SPECS",

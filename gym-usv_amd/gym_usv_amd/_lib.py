@@ -104,7 +104,7 @@ class UsvRolloutFrames(ctypes.Structure):
 
 class UsvSde(ctypes.Structure):
     """usv_sde: shape, generator key and Box bounds of the fused gSDE head (usv_sde_sample / usv_sde_weights /
-    usv_sde_squash_forward / _backward)."""
+    usv_sde_squash_forward / _backward / usv_sde_eval_forward / _backward)."""
     _fields_ = [("n", ctypes.c_int32), ("latent_dim", ctypes.c_int32), ("act_dim", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("gid0", ctypes.c_uint64),
                 ("low", ctypes.c_float * 4), ("high", ctypes.c_float * 4)]
@@ -125,7 +125,7 @@ class UsvReplay(ctypes.Structure):
 
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
-_i64, _u32 = ctypes.c_int64, ctypes.c_uint32
+_i64, _u32, _f32 = ctypes.c_int64, ctypes.c_uint32, ctypes.c_float
 SIGNATURES = [
     ("usv_abi_version", ctypes.c_int, []),
     ("usv_last_error", ctypes.c_char_p, []),
@@ -178,6 +178,11 @@ SIGNATURES = [
     ("usv_sde_squash_scratch_floats", _sz, [ctypes.POINTER(UsvSde)]),
     ("usv_sde_squash_backward", ctypes.c_int, [ctypes.POINTER(UsvSde), _u32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _sz, _vp, _vp, _vp]),
+    ("usv_sde_eval_forward", ctypes.c_int, [ctypes.POINTER(UsvSde), _i32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _f32, _vp,
+                                            _vp, _vp, _vp, _vp]),
+    ("usv_sde_eval_scratch_floats", _sz, [ctypes.POINTER(UsvSde), _i32]),
+    ("usv_sde_eval_backward", ctypes.c_int, [ctypes.POINTER(UsvSde), _i32, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _f32,
+                                             _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("usv_replay_put_obs", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _sz, _vp, _vp]),
     ("usv_replay_put_step", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("usv_replay_gather", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

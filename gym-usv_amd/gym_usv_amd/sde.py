@@ -20,7 +20,9 @@ launch that uses it.  ``reset_noise`` only increments ``epoch``.  ``weights(std)
 inspection, tests and checkpoints; a one-hot latent row makes ``sample`` return a row of it bit for bit.
 
 The arithmetic is float32 in the order gym-usv_amd/csrc/usv_sde_math.hpp fixes; tests/sde_ref.py restates
-it in float64.  PPO's update-time ``log_prob`` and its gradient stay torch autograd: they never needed W.
+it in float64.  PPO's update-time ``log_prob`` never needed W; ``DeviceSDE.evaluate`` is SB3's
+``evaluate_actions`` for stored actions with PPO's clipped surrogate on the same row and a HIP backward
+(``usv_sde_eval_forward`` / ``_backward``): one launch forward, two backward, in place of some tens each way.
 
 SAC differentiates through the sample, so ``DeviceSDE.squashed`` is the same head with ``squash_output=True``
 and a HIP backward (``usv_sde_squash_forward`` / ``_backward``): the backward rebuilds the normals from the
@@ -40,6 +42,7 @@ from ._lib import ptr as _ptr
 MAX_LATENT = 4096
 
 SquashedSample = collections.namedtuple("SquashedSample", "actions env_actions log_prob gaussian_actions")
+Evaluation = collections.namedtuple("Evaluation", "log_prob surrogate ratio")
 
 
 class _Squashed(torch.autograd.Function):
@@ -72,6 +75,41 @@ class _Squashed(torch.autograd.Function):
         head._squash_backward(ctx.epoch, mean, latent, std, gauss, var, g_act, g_logp, g_mean, g_lat, g_std)
         need = ctx.needs_input_grad
         return None, g_mean if need[1] else None, g_lat if need[2] else None, g_std if need[3] else None
+
+
+class _Evaluate(torch.autograd.Function):
+    """``DeviceSDE.evaluate`` under autograd: fresh outputs, ``var`` and ``ratio`` saved beside the inputs, the
+    backward is ``usv_sde_eval_backward``.  Without the PPO arguments ``surrogate`` and ``ratio`` are None."""
+
+    @staticmethod
+    def forward(ctx, head, mean, latent, std, actions, old_log_prob, advantages, clip_range):
+        B, A = mean.shape[0], head.act_dim
+        f4 = dict(dtype=torch.float32, device=head.device)
+        ppo = old_log_prob is not None
+        logp, var = torch.empty((B,), **f4), torch.empty((B, A), **f4)
+        sur, ratio = (torch.empty((B,), **f4), torch.empty((B,), **f4)) if ppo else (None, None)
+        head._eval_forward(mean, latent, std, actions, old_log_prob, advantages, clip_range, logp, sur, ratio, var)
+        ctx.head, ctx.clip = head, clip_range
+        ctx.save_for_backward(mean, latent, std, actions, var, ratio, advantages)
+        if ppo:
+            ctx.mark_non_differentiable(ratio)
+        ctx.set_materialize_grads(False)                    # an unused output's gradient stays None: NULL, zeros
+        return logp, sur, ratio
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_logp, g_sur, g_ratio):
+        head = ctx.head
+        mean, latent, std, actions, var, ratio, adv = ctx.saved_tensors
+        B, L, A = mean.shape[0], head.latent_dim, head.act_dim
+        f4 = dict(dtype=torch.float32, device=head.device)
+        need = ctx.needs_input_grad
+        g_logp = None if g_logp is None else g_logp.contiguous()
+        g_sur = None if g_sur is None else g_sur.contiguous()
+        g_mean, g_std = torch.empty((B, A), **f4), torch.empty((L, A), **f4)
+        g_lat = torch.empty((B, L), **f4) if need[2] else None
+        head._eval_backward(mean, latent, std, actions, var, ratio, adv, ctx.clip, g_logp, g_sur, g_mean, g_lat, g_std)
+        return None, g_mean if need[1] else None, g_lat, g_std if need[3] else None, None, None, None, None
 
 
 class DeviceSDE:
@@ -118,6 +156,7 @@ class DeviceSDE:
         f4 = dict(dtype=torch.float32, device=device)
         self._out = (torch.zeros((n, A), **f4), torch.zeros((n, A), **f4), torch.zeros((n,), **f4))
         self._sq_out = self._scratch = None                # squashed's buffers, made by its first call
+        self._eval_scratch = None                           # evaluate's backward scratch, grown with B
 
     @property
     def epoch(self):
@@ -170,9 +209,9 @@ class DeviceSDE:
                                             _lib.stream_ptr(self.device)), self.lib)
         return out
 
-    def _latent_stride(self, name, t):
-        return _lib.check_rows(name, t, torch.float32, (self.n, self.latent_dim), self.device, stride_multiple=4,
-                               align=16)
+    def _latent_stride(self, name, t, n=None):
+        return _lib.check_rows(name, t, torch.float32, (self.n if n is None else n, self.latent_dim), self.device,
+                               stride_multiple=4, align=16)
 
     def _squash_forward(self, mean, latent, std, out):
         n, L, A = self.n, self.latent_dim, self.act_dim
@@ -231,3 +270,74 @@ class DeviceSDE:
         if self.copy:
             return SquashedSample(act.clone(), env.clone(), logp.clone(), gauss.clone())
         return SquashedSample(act, env, logp, gauss)
+
+    def _eval_forward(self, mean, latent, std, actions, old_log_prob, advantages, clip_range, logp, sur, ratio, var):
+        B, L, A = mean.shape[0], self.latent_dim, self.act_dim
+        for name, t, shape in (("mean", mean, (B, A)), ("std", std, (L, A)), ("actions", actions, (B, A)),
+                               ("old_log_prob", old_log_prob, (B,)), ("advantages", advantages, (B,)),
+                               ("log_prob", logp, (B,)), ("surrogate", sur, (B,)), ("ratio", ratio, (B,)),
+                               ("var", var, (B, A))):
+            if t is not None:
+                _lib.check_tensor(name, t, torch.float32, shape, self.device)
+        _lib.check(self.lib.usv_sde_eval_forward(
+            self._sp, B, _ptr(mean), _ptr(latent), self._latent_stride("latent", latent, B), _ptr(std), _ptr(actions),
+            _ptr(old_log_prob), _ptr(advantages), 0.0 if clip_range is None else clip_range, _ptr(logp), _ptr(sur),
+            _ptr(ratio), _ptr(var), _lib.stream_ptr(self.device)), self.lib)
+
+    def _eval_backward(self, mean, latent, std, actions, var, ratio, advantages, clip_range, g_logp, g_sur, g_mean, g_lat,
+                       g_std):
+        B, L, A = mean.shape[0], self.latent_dim, self.act_dim
+        for name, t, shape in (("mean", mean, (B, A)), ("std", std, (L, A)), ("actions", actions, (B, A)),
+                               ("var", var, (B, A)), ("ratio", ratio, (B,)), ("advantages", advantages, (B,)),
+                               ("g_logp", g_logp, (B,)), ("g_sur", g_sur, (B,)), ("g_mean", g_mean, (B, A)),
+                               ("g_std", g_std, (L, A))):
+            if t is not None:
+                _lib.check_tensor(name, t, torch.float32, shape, self.device)
+        need = self.lib.usv_sde_eval_scratch_floats(self._sp, B)
+        if self._eval_scratch is None or self._eval_scratch.numel() < need:
+            self._eval_scratch = torch.empty((need,), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.usv_sde_eval_backward(
+            self._sp, B, _ptr(mean), _ptr(latent), self._latent_stride("latent", latent, B), _ptr(std), _ptr(actions),
+            _ptr(var), _ptr(ratio), _ptr(advantages), 0.0 if clip_range is None else clip_range, _ptr(g_logp), _ptr(g_sur),
+            _ptr(g_mean), _ptr(g_lat), 0 if g_lat is None else self._latent_stride("g_lat", g_lat, B), _ptr(g_std),
+            _ptr(self._eval_scratch), _lib.stream_ptr(self.device)), self.lib)
+
+    def evaluate(self, mean, latent, std, actions, old_log_prob=None, advantages=None, clip_range=None):
+        """PPO's update-time head, SB3's ``evaluate_actions`` for gSDE with the clipped surrogate on the same row:
+        ``Evaluation(log_prob, surrogate, ratio)`` with ``log_prob = Normal(mean, sqrt(latent^2 @ std^2 +
+        1e-6)).log_prob(actions).sum(-1)`` [B] (bit-equal to the ``logp`` that ``sample`` returned with these
+        actions), ``ratio = exp(log_prob - old_log_prob)`` [B] and ``surrogate = min(ratio * advantages,
+        clamp(ratio, 1 - clip_range, 1 + clip_range) * advantages)`` [B]: ``-surrogate.mean()`` is PPO's policy
+        loss.  ``old_log_prob``, ``advantages`` [B] and ``clip_range`` (a float >= 0) come together; without them
+        ``surrogate`` and ``ratio`` are None.
+
+        No noise is drawn: the call does not depend on ``num_envs``, the seed or the epoch, and ``B`` (``mean``'s
+        rows, >= 1) is the caller's: a short last minibatch is a smaller ``B``.  ``mean``, ``actions`` [B, A] and
+        ``std`` [L, A] are contiguous float32; ``latent`` [B, L] as for ``sample``.  The outputs are fresh tensors.
+
+        Under ``torch.no_grad()``, or when no input requires grad: one launch, nothing saved.  Otherwise a
+        ``torch.autograd.Function`` whose backward (once differentiable; two launches on the current stream)
+        returns the gradients of ``log_prob`` and ``surrogate`` with respect to ``mean``, ``std`` and, only where
+        it requires grad, ``latent`` (PPO's ``learn_features=False`` passes ``latent.detach()``, and nothing of
+        size [B, L] is then written).  ``ratio`` carries no gradient (it feeds ``approx_kl`` / ``clip_fraction``);
+        ``actions``, ``old_log_prob`` and ``advantages`` are data.  The gradient of ``std`` is summed over rows in a
+        fixed order without atomics: bitwise reproducible.  The backward's scratch belongs to the head and grows
+        with ``B``: backward calls of one head must be stream-ordered."""
+        given = [x is not None for x in (old_log_prob, advantages, clip_range)]
+        if any(given) and not all(given):
+            raise ValueError("old_log_prob, advantages and clip_range come together or not at all")
+        if mean.dim() != 2 or mean.shape[0] < 1:
+            raise ValueError("mean must be a [B, act_dim] tensor with B >= 1")
+        if clip_range is not None:
+            clip_range = float(clip_range)
+            if not clip_range >= 0.0:
+                raise ValueError("clip_range must be >= 0")
+        data = tuple(None if x is None else x.detach() for x in (actions, old_log_prob, advantages))
+        if torch.is_grad_enabled() and (mean.requires_grad or latent.requires_grad or std.requires_grad):
+            return Evaluation(*_Evaluate.apply(self, mean, latent, std, *data, clip_range))
+        B = mean.shape[0]
+        f4 = dict(dtype=torch.float32, device=self.device)
+        logp = torch.empty((B,), **f4)
+        sur, ratio = (torch.empty((B,), **f4), torch.empty((B,), **f4)) if all(given) else (None, None)
+        self._eval_forward(mean.detach(), latent.detach(), std.detach(), *data, clip_range, logp, sur, ratio, None)
+        return Evaluation(logp, sur, ratio)

@@ -593,6 +593,49 @@ int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean_
                             float* g_lat_dev, size_t g_lat_row_stride_floats, float* g_std_dev, float* scratch_dev,
                             void* stream);
 
+/* PPO's update-time head: SB3's ActorCriticPolicy.evaluate_actions for StateDependentNoiseDistribution (the
+ * log-probability of stored actions under the current policy, no noise) with PPO's clipped surrogate on the same
+ * row, and its backward.  Additive (ABI v5 addition); handle-free, stream-ordered, no host sync.  Of the usv_sde
+ * only latent_dim, act_dim and reserved (= 0) are read: no noise is drawn, so n, seed, gid0, the bounds and the
+ * epoch do not enter, and the row count is the call's `rows` (PPO's last minibatch may be short).
+ *
+ * usv_sde_eval_forward(s, rows, mean [rows][A], lat rows of latent_dim floats, row stride, std [latent_dim][A],
+ * act [rows][A], old_logp [rows] or NULL, adv [rows] or NULL, clip, logp [rows], sur [rows] or NULL, ratio [rows]
+ * or NULL, var [rows][A] or NULL), one launch:
+ *   var_k   = sum_j (lat_j lat_j) (std_jk std_jk)         <- proba_distribution: usv_sde_sample's var_k bit for bit
+ *   logp    = sum_k (-(act_k - mean_k)^2 / (2 s2_k) - 0.5 ln s2_k - 0.5 ln 2 pi),  s2_k = var_k + 1e-6
+ *                                                         <- log_prob: bit-equal to usv_sde_sample's logp for its act
+ * and, with old_logp, adv, sur and ratio (all four or none),
+ *   ratio   = exp(logp - old_logp)                        <- PPO.train: th.exp(log_prob - rollout_data.old_log_prob)
+ *   sur     = min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv)    <- policy_loss_1, policy_loss_2, th.min
+ * var is what the backward needs of the forward beyond its outputs; NULL on a call that is not differentiated.
+ *
+ * usv_sde_eval_backward(s, rows, mean, lat, row stride, std, act, var, ratio or NULL, adv or NULL, clip, g_logp
+ * [rows] or NULL, g_sur [rows] or NULL (NULL: zeros), g_mean [rows][A], g_lat rows of latent_dim floats or NULL, its
+ * row stride, g_std [latent_dim][A], scratch), two launches on the stream: the gradients of sum(g_logp logp) +
+ * sum(g_sur sur) with respect to mean, lat (through the variance; NULL where the latent is detached, PPO's default,
+ * and then nothing of [rows][latent_dim] is written) and std, as torch autograd gives them for Normal.log_prob, exp,
+ * clamp and min, ties included (csrc/usv_sde_math.hpp).  act, old_logp and adv are data: no gradient.  g_std's sum
+ * over rows is usv_sde_squash_backward's: no atomics, a fixed order, partials in scratch of
+ * usv_sde_eval_scratch_floats(s, rows) = P * latent_dim * act_dim floats (0 for arguments that would be refused).
+ * Two backward calls that share a scratch must be stream-ordered.
+ *
+ * USV_ERR_ARG, before any HIP call, for a NULL usv_sde, act_dim not 1 or 2, latent_dim outside [4, 4096] or not a
+ * multiple of 4, reserved != 0, rows <= 0, a row stride below latent_dim or not a multiple of 4 (lat; g_lat where
+ * set), only some of old_logp / adv / sur / ratio (forward) or of ratio / adv (backward), g_sur without ratio, a
+ * negative or NaN clip where the surrogate is asked for, a NULL scratch or other needed buffer, a lat, g_lat or
+ * scratch that is not 16-B aligned or another buffer that is not 4-B aligned.  Then the device-memory checks. */
+int usv_sde_eval_forward(const usv_sde* s, int32_t rows, const float* mean_dev, const float* lat_dev,
+                         size_t lat_row_stride_floats, const float* std_dev, const float* act_dev,
+                         const float* old_logp_dev, const float* adv_dev, float clip, float* logp_dev, float* sur_dev,
+                         float* ratio_dev, float* var_dev, void* stream);
+size_t usv_sde_eval_scratch_floats(const usv_sde* s, int32_t rows);
+int usv_sde_eval_backward(const usv_sde* s, int32_t rows, const float* mean_dev, const float* lat_dev,
+                          size_t lat_row_stride_floats, const float* std_dev, const float* act_dev, const float* var_dev,
+                          const float* ratio_dev, const float* adv_dev, float clip, const float* g_logp_dev,
+                          const float* g_sur_dev, float* g_mean_dev, float* g_lat_dev, size_t g_lat_row_stride_floats,
+                          float* g_std_dev, float* scratch_dev, void* stream);
+
 /* Device replay buffer: SB3's ReplayBuffer (common/buffers.py: add, sample, _get_samples with
  * optimize_memory_usage=False and handle_timeout_termination=True) and the terminal-observation
  * substitution of OffPolicyAlgorithm._store_transition, for windows of k frames of d floats that evolve by
