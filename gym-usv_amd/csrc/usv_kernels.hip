@@ -24,8 +24,9 @@
 //   usv_rollout_frames_math.hpp  frame-deduplicated obs storage: rows, live mask, clear rule (host C++, no HIP)
 //   usv_rollout_frames.hpp  frame store and minibatch gather (usv_rollout_put_obs_frames / usv_rollout_gather)
 //   usv_sde_math.hpp      gSDE head: Philox numbering, Box-Muller, sums, clip, log-probability (host C++, no HIP)
-//   usv_sde.hpp           fused gSDE action head (usv_sde_sample / usv_sde_weights / usv_sde_squash_forward / _backward /
-//                         usv_sde_eval_forward / _backward)
+//   usv_sde.hpp           gSDE heads: one row loop under the three forwards, the two backwards, weights
+//                         (usv_sde_sample / usv_sde_weights / usv_sde_squash_forward / _backward / usv_sde_eval_forward /
+//                         _backward)
 //   usv_replay_math.hpp   replay buffer: slots, frame rows, age and live masks (host C++, no HIP)
 //   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
@@ -1227,19 +1228,37 @@ int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, cons
   return USV_OK;
 }
 
-// ---- fused gSDE action head (usv_sde.hpp)
-// The checks of a usv_sde that need no HIP call; fills the kernels' arguments.
-static int sde_check(const usv_sde* s, SdeArgs& a) {
+// ---- gSDE heads (usv_sde.hpp)
+// The checks that need no HIP call.  sde_shape: what every entry needs of a usv_sde; sde_check: a head that draws
+// noise, fills the kernels' arguments; sde_eval_check: the evaluation (the struct's n, key and bounds are not its).
+static int sde_shape(const usv_sde* s) {
   if (!s) return fail(USV_ERR_ARG, "null usv_sde");
-  if (s->n <= 0) return fail(USV_ERR_ARG, "usv_sde: n must be > 0");
   if (s->act_dim != 1 && s->act_dim != 2) return fail(USV_ERR_ARG, "usv_sde: act_dim must be 1 or 2");
   if (!sde_latent_ok(s->latent_dim))
     return fail(USV_ERR_ARG, "usv_sde: latent_dim must be a multiple of 4 in [4, 4096]");
   if (s->reserved != 0) return fail(USV_ERR_ARG, "usv_sde: reserved must be 0");
+  return USV_OK;
+}
+
+static int sde_check(const usv_sde* s, uint32_t epoch, SdeArgs& a) {
+  if (s && s->n <= 0) return fail(USV_ERR_ARG, "usv_sde: n must be > 0");
+  if (int rc = sde_shape(s)) return rc;
   for (int k = 0; k < s->act_dim; ++k)
     if (!(s->low[k] <= s->high[k])) return fail(USV_ERR_ARG, "usv_sde: low must be <= high (and neither NaN)");
-  a = SdeArgs{s->n, s->latent_dim, 0u, s->seed, s->gid0, {s->low[0], s->low[1]}, {s->high[0], s->high[1]}};
+  a = SdeArgs{s->n, s->latent_dim, epoch, s->seed, s->gid0, {s->low[0], s->low[1]}, {s->high[0], s->high[1]}};
   return USV_OK;
+}
+
+static int sde_eval_check(const usv_sde* s, int32_t rows) {
+  if (int rc = sde_shape(s)) return rc;
+  if (rows <= 0) return fail(USV_ERR_ARG, "usv_sde_eval: rows must be > 0");
+  return USV_OK;
+}
+
+// A row stride (`what`: which, where an entry has two) of entry `fn`.
+static int sde_stride(const usv_sde* s, size_t stride, const char* fn, const char* what = "") {
+  if (stride >= (size_t)s->latent_dim && stride % 4 == 0) return USV_OK;
+  return fail(USV_ERR_ARG, std::string(fn) + ": the " + what + "row stride must be a multiple of 4 and >= latent_dim");
 }
 
 static int sde_bufs(const Buf* b, size_t nb, int& dev) {
@@ -1254,44 +1273,59 @@ static int sde_bufs(const Buf* b, size_t nb, int& dev) {
   return USV_OK;
 }
 
+static size_t sde_scratch_floats(int64_t rows, const usv_sde* s) {
+  return (size_t)sde_partials(rows) * (size_t)s->latent_dim * (size_t)s->act_dim;
+}
+
+static int64_t sde_wave_blocks(int64_t waves) { return (waves + kWaves - 1) / kWaves; }
+
+extern "C++" {
+// k1 / k2, the kernel's act_dim = 1 / 2 instance, on `blocks` blocks.
+template <class K, class... Q>
+static int sde_launch(const usv_sde* s, K k1, K k2, int64_t blocks, void* stream, Q... args) {
+  hipLaunchKernelGGL(s->act_dim == 1 ? k1 : k2, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, args...);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// A backward of `rows` rows, a wave per partial, then g_std from the partials in scratch.
+template <class K, class... Q>
+static int sde_launch_backward(const usv_sde* s, K k1, K k2, int64_t rows, float* scratch, float* g_std, void* stream,
+                               Q... args) {
+  const int partials = (int)sde_partials(rows), LA = s->latent_dim * s->act_dim;
+  if (int rc = sde_launch(s, k1, k2, sde_wave_blocks(partials), stream, args...)) return rc;
+  hipLaunchKernelGGL(sde_std_finalise_kernel, dim3((unsigned)((LA + 15) / 16)), dim3(kBlock), 0, (hipStream_t)stream,
+                     partials, LA, scratch, g_std);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+}  // extern "C++"
+
 int usv_sde_sample(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
                    const float* std, float* act, float* act_env, float* logp, void* stream) {
   SdeArgs a;
   int dev;
-  if (int rc = sde_check(s, a)) return rc;
-  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
-    return fail(USV_ERR_ARG, "usv_sde_sample: the row stride must be a multiple of 4 and >= latent_dim");
+  if (int rc = sde_check(s, epoch, a)) return rc;
+  if (int rc = sde_stride(s, stride, "usv_sde_sample")) return rc;
   const Buf all[] = {{lat, 16}, {mean, 4}, {std, 4}, {act, 4}, {act_env, 4}, {logp, 4}};
   if (int rc = sde_bufs(all, 6, dev)) return rc;
-  a.epoch = epoch;
   DeviceGuard g(dev);
-  const dim3 grid((unsigned)(((int64_t)a.n + kWaves - 1) / kWaves)), block(kBlock);
-  if (s->act_dim == 1)
-    hipLaunchKernelGGL(sde_sample_kernel<1>, grid, block, 0, (hipStream_t)stream, a, mean, lat, stride, std, act, act_env, logp);
-  else
-    hipLaunchKernelGGL(sde_sample_kernel<2>, grid, block, 0, (hipStream_t)stream, a, mean, lat, stride, std, act, act_env, logp);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return sde_launch(s, sde_sample_kernel<1>, sde_sample_kernel<2>, sde_wave_blocks(a.n), stream, a, mean, lat, stride,
+                    std, act, act_env, logp);
 }
 
 int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std, float* w, void* stream) {
   SdeArgs a;
   int dev;
-  if (int rc = sde_check(s, a)) return rc;
+  if (int rc = sde_check(s, epoch, a)) return rc;
   const int64_t threads = (int64_t)a.n * (a.L * s->act_dim / 4);
   if ((threads + kBlock - 1) / kBlock > 2147483647)
     return fail(USV_ERR_ARG, "usv_sde_weights: n * latent_dim * act_dim / 4 is above 2^31 - 1 blocks of 256");
   const Buf all[] = {{w, 4}, {std, 4}};
   if (int rc = sde_bufs(all, 2, dev)) return rc;
-  a.epoch = epoch;
   DeviceGuard g(dev);
-  const dim3 grid((unsigned)((threads + kBlock - 1) / kBlock)), block(kBlock);
-  if (s->act_dim == 1)
-    hipLaunchKernelGGL(sde_weights_kernel<1>, grid, block, 0, (hipStream_t)stream, a, std, w);
-  else
-    hipLaunchKernelGGL(sde_weights_kernel<2>, grid, block, 0, (hipStream_t)stream, a, std, w);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return sde_launch(s, sde_weights_kernel<1>, sde_weights_kernel<2>, (threads + kBlock - 1) / kBlock, stream, a, std,
+                    w);
 }
 
 int usv_sde_squash_forward(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
@@ -1299,30 +1333,20 @@ int usv_sde_squash_forward(const usv_sde* s, uint32_t epoch, const float* mean, 
                            void* stream) {
   SdeArgs a;
   int dev;
-  if (int rc = sde_check(s, a)) return rc;
-  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
-    return fail(USV_ERR_ARG, "usv_sde_squash_forward: the row stride must be a multiple of 4 and >= latent_dim");
+  if (int rc = sde_check(s, epoch, a)) return rc;
+  if (int rc = sde_stride(s, stride, "usv_sde_squash_forward")) return rc;
   if ((gauss == nullptr) != (var == nullptr))
     return fail(USV_ERR_ARG, "usv_sde_squash_forward: gauss and var must be both NULL or both set");
   const Buf all[] = {{lat, 16}, {mean, 4}, {std, 4}, {act, 4}, {act_env, 4}, {logp, 4}, {gauss, 4, true}, {var, 4, true}};
   if (int rc = sde_bufs(all, 8, dev)) return rc;
-  a.epoch = epoch;
   DeviceGuard g(dev);
-  const dim3 grid((unsigned)(((int64_t)a.n + kWaves - 1) / kWaves)), block(kBlock);
-  if (s->act_dim == 1)
-    hipLaunchKernelGGL(sde_squash_forward_kernel<1>, grid, block, 0, (hipStream_t)stream, a, mean, lat, stride, std, act,
-                       act_env, logp, gauss, var);
-  else
-    hipLaunchKernelGGL(sde_squash_forward_kernel<2>, grid, block, 0, (hipStream_t)stream, a, mean, lat, stride, std, act,
-                       act_env, logp, gauss, var);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return sde_launch(s, sde_squash_forward_kernel<1>, sde_squash_forward_kernel<2>, sde_wave_blocks(a.n), stream, a,
+                    mean, lat, stride, std, act, act_env, logp, gauss, var);
 }
 
 size_t usv_sde_squash_scratch_floats(const usv_sde* s) {
   SdeArgs a;
-  if (sde_check(s, a)) return 0;
-  return (size_t)sde_partials(a.n) * (size_t)a.L * (size_t)s->act_dim;
+  return sde_check(s, 0u, a) ? 0 : sde_scratch_floats(a.n, s);
 }
 
 int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
@@ -1331,42 +1355,17 @@ int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean,
                             float* scratch, void* stream) {
   SdeArgs a;
   int dev;
-  if (int rc = sde_check(s, a)) return rc;
-  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
-    return fail(USV_ERR_ARG, "usv_sde_squash_backward: the row stride must be a multiple of 4 and >= latent_dim");
-  if (g_stride < (size_t)s->latent_dim || g_stride % 4 != 0)
-    return fail(USV_ERR_ARG, "usv_sde_squash_backward: the g_lat row stride must be a multiple of 4 and >= latent_dim");
+  if (int rc = sde_check(s, epoch, a)) return rc;
+  if (int rc = sde_stride(s, stride, "usv_sde_squash_backward")) return rc;
+  if (int rc = sde_stride(s, g_stride, "usv_sde_squash_backward", "g_lat ")) return rc;
   if (!scratch) return fail(USV_ERR_ARG, "usv_sde_squash_backward: null scratch");
   const Buf all[] = {{lat, 16},  {g_lat, 16}, {scratch, 16},      {mean, 4},           {std, 4},   {gauss, 4},
                      {var, 4},   {g_mean, 4}, {g_act, 4, true},   {g_logp, 4, true},   {g_std, 4}};
   if (int rc = sde_bufs(all, 11, dev)) return rc;
-  a.epoch = epoch;
   DeviceGuard g(dev);
-  const int R = (int)sde_rows_per_partial(a.n), P = (int)sde_partials(a.n), LA = a.L * s->act_dim;
-  const dim3 grid((unsigned)((P + kWaves - 1) / kWaves)), block(kBlock);
-  if (s->act_dim == 1)
-    hipLaunchKernelGGL(sde_squash_backward_kernel<1>, grid, block, 0, (hipStream_t)stream, a, R, mean, lat, stride, std,
-                       gauss, var, g_act, g_logp, g_mean, g_lat, g_stride, scratch);
-  else
-    hipLaunchKernelGGL(sde_squash_backward_kernel<2>, grid, block, 0, (hipStream_t)stream, a, R, mean, lat, stride, std,
-                       gauss, var, g_act, g_logp, g_mean, g_lat, g_stride, scratch);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(sde_std_finalise_kernel, dim3((unsigned)((LA + 15) / 16)), block, 0, (hipStream_t)stream, P, LA,
-                     scratch, g_std);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
-}
-
-// The checks of usv_sde_eval_* that need no HIP call: the struct's shape (its n, key and bounds are not the
-// evaluation's) and the call's row count.
-static int sde_eval_check(const usv_sde* s, int32_t rows) {
-  if (!s) return fail(USV_ERR_ARG, "null usv_sde");
-  if (s->act_dim != 1 && s->act_dim != 2) return fail(USV_ERR_ARG, "usv_sde: act_dim must be 1 or 2");
-  if (!sde_latent_ok(s->latent_dim))
-    return fail(USV_ERR_ARG, "usv_sde: latent_dim must be a multiple of 4 in [4, 4096]");
-  if (s->reserved != 0) return fail(USV_ERR_ARG, "usv_sde: reserved must be 0");
-  if (rows <= 0) return fail(USV_ERR_ARG, "usv_sde_eval: rows must be > 0");
-  return USV_OK;
+  return sde_launch_backward(s, sde_squash_backward_kernel<1>, sde_squash_backward_kernel<2>, a.n, scratch, g_std,
+                             stream, a, (int)sde_rows_per_partial(a.n), mean, lat, stride, std, gauss, var, g_act, g_logp,
+                             g_mean, g_lat, g_stride, scratch);
 }
 
 int usv_sde_eval_forward(const usv_sde* s, int32_t rows, const float* mean, const float* lat, size_t stride,
@@ -1374,8 +1373,7 @@ int usv_sde_eval_forward(const usv_sde* s, int32_t rows, const float* mean, cons
                          float* logp, float* sur, float* ratio, float* var, void* stream) {
   int dev;
   if (int rc = sde_eval_check(s, rows)) return rc;
-  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
-    return fail(USV_ERR_ARG, "usv_sde_eval_forward: the row stride must be a multiple of 4 and >= latent_dim");
+  if (int rc = sde_stride(s, stride, "usv_sde_eval_forward")) return rc;
   const bool ppo = old_logp != nullptr;
   if ((adv != nullptr) != ppo || (sur != nullptr) != ppo || (ratio != nullptr) != ppo)
     return fail(USV_ERR_ARG, "usv_sde_eval_forward: old_logp, adv, sur and ratio must be all NULL or all set");
@@ -1384,20 +1382,12 @@ int usv_sde_eval_forward(const usv_sde* s, int32_t rows, const float* mean, cons
                      {old_logp, 4, true}, {adv, 4, true}, {sur, 4, true}, {ratio, 4, true}, {var, 4, true}};
   if (int rc = sde_bufs(all, 10, dev)) return rc;
   DeviceGuard g(dev);
-  const dim3 grid((unsigned)(((int64_t)rows + kWaves - 1) / kWaves)), block(kBlock);
-  if (s->act_dim == 1)
-    hipLaunchKernelGGL(sde_eval_forward_kernel<1>, grid, block, 0, (hipStream_t)stream, (int)rows, s->latent_dim, mean, lat,
-                       stride, std, act, old_logp, adv, clip, logp, sur, ratio, var);
-  else
-    hipLaunchKernelGGL(sde_eval_forward_kernel<2>, grid, block, 0, (hipStream_t)stream, (int)rows, s->latent_dim, mean, lat,
-                       stride, std, act, old_logp, adv, clip, logp, sur, ratio, var);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return sde_launch(s, sde_eval_forward_kernel<1>, sde_eval_forward_kernel<2>, sde_wave_blocks(rows), stream,
+                    (int)rows, s->latent_dim, mean, lat, stride, std, act, old_logp, adv, clip, logp, sur, ratio, var);
 }
 
 size_t usv_sde_eval_scratch_floats(const usv_sde* s, int32_t rows) {
-  if (sde_eval_check(s, rows)) return 0;
-  return (size_t)sde_partials(rows) * (size_t)s->latent_dim * (size_t)s->act_dim;
+  return sde_eval_check(s, rows) ? 0 : sde_scratch_floats(rows, s);
 }
 
 int usv_sde_eval_backward(const usv_sde* s, int32_t rows, const float* mean, const float* lat, size_t stride,
@@ -1406,10 +1396,9 @@ int usv_sde_eval_backward(const usv_sde* s, int32_t rows, const float* mean, con
                           size_t g_stride, float* g_std, float* scratch, void* stream) {
   int dev;
   if (int rc = sde_eval_check(s, rows)) return rc;
-  if (stride < (size_t)s->latent_dim || stride % 4 != 0)
-    return fail(USV_ERR_ARG, "usv_sde_eval_backward: the row stride must be a multiple of 4 and >= latent_dim");
-  if (g_lat && (g_stride < (size_t)s->latent_dim || g_stride % 4 != 0))
-    return fail(USV_ERR_ARG, "usv_sde_eval_backward: the g_lat row stride must be a multiple of 4 and >= latent_dim");
+  if (int rc = sde_stride(s, stride, "usv_sde_eval_backward")) return rc;
+  if (g_lat)
+    if (int rc = sde_stride(s, g_stride, "usv_sde_eval_backward", "g_lat ")) return rc;
   if ((ratio != nullptr) != (adv != nullptr))
     return fail(USV_ERR_ARG, "usv_sde_eval_backward: ratio and adv must be both NULL or both set");
   if (g_sur && !ratio) return fail(USV_ERR_ARG, "usv_sde_eval_backward: g_sur needs ratio and adv");
@@ -1420,19 +1409,9 @@ int usv_sde_eval_backward(const usv_sde* s, int32_t rows, const float* mean, con
                      {adv, 4, true},  {g_logp, 4, true}, {g_sur, 4, true}};
   if (int rc = sde_bufs(all, 13, dev)) return rc;
   DeviceGuard g(dev);
-  const int R = (int)sde_rows_per_partial(rows), P = (int)sde_partials(rows), LA = s->latent_dim * s->act_dim;
-  const dim3 grid((unsigned)((P + kWaves - 1) / kWaves)), block(kBlock);
-  if (s->act_dim == 1)
-    hipLaunchKernelGGL(sde_eval_backward_kernel<1>, grid, block, 0, (hipStream_t)stream, (int)rows, s->latent_dim, R, mean,
-                       lat, stride, std, act, var, ratio, adv, clip, g_logp, g_sur, g_mean, g_lat, g_stride, scratch);
-  else
-    hipLaunchKernelGGL(sde_eval_backward_kernel<2>, grid, block, 0, (hipStream_t)stream, (int)rows, s->latent_dim, R, mean,
-                       lat, stride, std, act, var, ratio, adv, clip, g_logp, g_sur, g_mean, g_lat, g_stride, scratch);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(sde_std_finalise_kernel, dim3((unsigned)((LA + 15) / 16)), block, 0, (hipStream_t)stream, P, LA,
-                     scratch, g_std);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return sde_launch_backward(s, sde_eval_backward_kernel<1>, sde_eval_backward_kernel<2>, rows, scratch, g_std,
+                             stream, (int)rows, s->latent_dim, (int)sde_rows_per_partial(rows), mean, lat, stride, std, act,
+                             var, ratio, adv, clip, g_logp, g_sur, g_mean, g_lat, g_stride, scratch);
 }
 
 // ---- device replay buffer (usv_replay.hpp)

@@ -53,7 +53,7 @@
 // balanced binary tree in strand order, neighbours first (sde_partials_sum).
 //
 // The evaluation head (usv_sde_eval_forward / _backward: PPO's evaluate_actions, no noise).  For stored actions
-// act_k, var_k as above (sde_var_accum: sample's terms, lanes and tree, so sample's bits), then
+// act_k, var_k as above (sde_var_accum, the variance line of sde_accum: sample's terms, lanes and tree), then
 //   logp  = sum_k sde_logp_term(act_k, mean_k, var_k),  k ascending from 0.0f
 // and, where old, adv and the clip range c are given (sde_ppo_surrogate),
 //   ratio = expf(logp - old);  rc = min(max(ratio, 1 - c), 1 + c);  s1 = ratio adv;  s2 = rc adv
@@ -65,6 +65,7 @@
 //   gv_k    = t ((d_k d_k) / ((2 s2v_k) s2v_k) - 0.5 / s2v_k)
 //   g_lat_j  = fmaf(gv_k, (2 lat_j)(std_jk std_jk), .)     k ascending from +0.0f
 //   g_std_jk = fmaf(gv_k, (2 (lat_j lat_j)) std_jk, .)     rows ascending, partials and their sum as above
+// (sde_eval_grad_accum alone).
 #pragma once
 
 #include <math.h>
@@ -145,14 +146,19 @@ USV_SDE_HD void sde_normals(const uint32_t (&o)[4], float (&z)[4]) {
 
 USV_SDE_HD float sde_weight(float std, float z) { return std * z; }
 
-// One term of a lane's two accumulations.
-USV_SDE_HD void sde_accum(float lat, float std, float w, float& noise, float& var) {
+// One term of a lane's variance sum.
+USV_SDE_HD void sde_var_accum(float lat, float std, float& var) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
   const float l2 = lat * lat, s2 = std * std;
-  noise = fmaf(lat, w, noise);
   var = fmaf(l2, s2, var);
+}
+
+// One term of a lane's two accumulations.
+USV_SDE_HD void sde_accum(float lat, float std, float w, float& noise, float& var) {
+  noise = fmaf(lat, w, noise);
+  sde_var_accum(lat, std, var);
 }
 
 // The 64 lane sums by the balanced tree; p is overwritten.
@@ -218,6 +224,14 @@ USV_SDE_HD float sde_squash_logp_term(float u, float mean, float var, float om) 
   return sde_logp_term(u, mean, var) - logf(om + kSdeEps);
 }
 
+// The gradient of var_k for the row's upstream t of logp: t ((d d) / ((2 s2) s2) - 0.5 / s2).
+USV_SDE_HD float sde_var_grad(float t, float d, float s2) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return t * ((d * d) / ((2.0f * s2) * s2) - 0.5f / s2);
+}
+
 // One action's row gradients from the saved u and var: G (= g_mean), gn (of noise_k), gv (of var_k).
 USV_SDE_HD void sde_squash_grad_tail(float u, float mean, float var, float ga, float gl, float& G, float& gn,
                                      float& gv) {
@@ -232,10 +246,25 @@ USV_SDE_HD void sde_squash_grad_tail(float u, float mean, float var, float ga, f
   const float lg = ((2.0f * a) * om) / c;
   G = ga * om + gl * lg;
   gn = G - (gl * d) / s2;
-  gv = gl * ((d * d) / ((2.0f * s2) * s2) - 0.5f / s2);
+  gv = sde_var_grad(gl, d, s2);
 }
 
-// One matrix element's terms of g_lat_j and g_std_jk.
+// One matrix element's terms of g_lat_j and g_std_jk through the variance alone (the evaluation head's).
+USV_SDE_HD void sde_eval_grad_accum(float lat, float std, float gv, float& g_lat, float& g_std) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float vl = (2.0f * lat) * (std * std);
+  const float vs = (2.0f * (lat * lat)) * std;
+  g_lat = fmaf(gv, vl, g_lat);
+  g_std = fmaf(gv, vs, g_std);
+}
+
+// One matrix element's terms of g_lat_j and g_std_jk through the noise and the variance.  Its variance terms are
+// sde_eval_grad_accum's, written out here: composed of a noise half and that function, the same arithmetic reaches
+// the vectoriser in another order and sde_squash_backward_kernel<2> compiles to 614 instructions for 613, and the
+// squashed update at 65 536 x 256 measured 0.5 % above the parent's slowest process (profiles/sde_refactor_ab.json,
+// "composed_grad_accum").
 USV_SDE_HD void sde_grad_accum(float lat, float std, float z, float gn, float gv, float& g_lat, float& g_std) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -264,15 +293,6 @@ USV_SDE_HD float sde_partials_sum(const float* part, size_t stride, int P) {
 }
 
 // ---- the evaluation head (PPO's evaluate_actions, usv_sde_eval_forward / _backward)
-// One term of a lane's variance sum: sde_accum's second line, so var_k is sample's bit for bit.
-USV_SDE_HD void sde_var_accum(float lat, float std, float& var) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  const float l2 = lat * lat, s2 = std * std;
-  var = fmaf(l2, s2, var);
-}
-
 // torch.clamp(ratio, 1 - c, 1 + c): a NaN ratio stays NaN.
 USV_SDE_HD float sde_ppo_clamp(float ratio, float clip) {
 #if defined(__clang__)
@@ -316,7 +336,7 @@ USV_SDE_HD float sde_eval_row_grad(float gl, float gs, float ratio, float adv, f
   return gl + (s1 <= s2 ? gs * s1 : 0.0f);
 }
 
-// One action's gradients from the row's t (sde_eval_row_grad): g_mean_k and gv (of var_k; sde_squash_grad_tail's).
+// One action's gradients from the row's t (sde_eval_row_grad): g_mean_k and gv (of var_k).
 USV_SDE_HD void sde_eval_grad_tail(float act, float mean, float var, float t, float& g_mean, float& gv) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -324,18 +344,7 @@ USV_SDE_HD void sde_eval_grad_tail(float act, float mean, float var, float t, fl
   const float s2 = var + kSdeEps;
   const float d = act - mean;
   g_mean = (t * d) / s2;
-  gv = t * ((d * d) / ((2.0f * s2) * s2) - 0.5f / s2);
-}
-
-// One matrix element's terms of g_lat_j and g_std_jk: the variance half of sde_grad_accum.
-USV_SDE_HD void sde_eval_grad_accum(float lat, float std, float gv, float& g_lat, float& g_std) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  const float vl = (2.0f * lat) * (std * std);
-  const float vs = (2.0f * (lat * lat)) * std;
-  g_lat = fmaf(gv, vl, g_lat);
-  g_std = fmaf(gv, vs, g_std);
+  gv = sde_var_grad(t, d, s2);
 }
 
 }  // namespace usv

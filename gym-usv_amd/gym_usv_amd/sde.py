@@ -45,6 +45,16 @@ SquashedSample = collections.namedtuple("SquashedSample", "actions env_actions l
 Evaluation = collections.namedtuple("Evaluation", "log_prob surrogate ratio")
 
 
+def _fresh(head, *shapes, make=torch.empty):
+    """Fresh float32 tensors of ``shapes`` on the head's device."""
+    return tuple(make(s, dtype=torch.float32, device=head.device) for s in shapes)
+
+
+def _contiguous(*tensors):
+    """Each tensor contiguous; None (an unused output's gradient: NULL, zeros) stays None."""
+    return tuple(None if t is None else t.contiguous() for t in tensors)
+
+
 class _Squashed(torch.autograd.Function):
     """``DeviceSDE.squashed`` under autograd: the forward writes fresh tensors (the saved ``gauss`` / ``var`` must
     outlive the head's next call), the backward is ``usv_sde_squash_backward`` with the forward's epoch."""
@@ -52,9 +62,7 @@ class _Squashed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, mean, latent, std):
         n, A = head.n, head.act_dim
-        f4 = dict(dtype=torch.float32, device=head.device)
-        act, env, gauss, var = (torch.empty((n, A), **f4) for _ in range(4))
-        logp = torch.empty((n,), **f4)
+        act, env, gauss, var, logp = _fresh(head, (n, A), (n, A), (n, A), (n, A), (n,))
         head._squash_forward(mean, latent, std, (act, env, logp, gauss, var))
         ctx.head, ctx.epoch = head, head._epoch
         ctx.save_for_backward(mean, latent, std, gauss, var)
@@ -68,10 +76,8 @@ class _Squashed(torch.autograd.Function):
         head = ctx.head
         mean, latent, std, gauss, var = ctx.saved_tensors
         n, L, A = head.n, head.latent_dim, head.act_dim
-        f4 = dict(dtype=torch.float32, device=head.device)
-        g_act = None if g_act is None else g_act.contiguous()
-        g_logp = None if g_logp is None else g_logp.contiguous()
-        g_mean, g_lat, g_std = torch.empty((n, A), **f4), torch.empty((n, L), **f4), torch.empty((L, A), **f4)
+        g_act, g_logp = _contiguous(g_act, g_logp)
+        g_mean, g_lat, g_std = _fresh(head, (n, A), (n, L), (L, A))
         head._squash_backward(ctx.epoch, mean, latent, std, gauss, var, g_act, g_logp, g_mean, g_lat, g_std)
         need = ctx.needs_input_grad
         return None, g_mean if need[1] else None, g_lat if need[2] else None, g_std if need[3] else None
@@ -84,10 +90,9 @@ class _Evaluate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, mean, latent, std, actions, old_log_prob, advantages, clip_range):
         B, A = mean.shape[0], head.act_dim
-        f4 = dict(dtype=torch.float32, device=head.device)
         ppo = old_log_prob is not None
-        logp, var = torch.empty((B,), **f4), torch.empty((B, A), **f4)
-        sur, ratio = (torch.empty((B,), **f4), torch.empty((B,), **f4)) if ppo else (None, None)
+        logp, var = _fresh(head, (B,), (B, A))
+        sur, ratio = _fresh(head, (B,), (B,)) if ppo else (None, None)
         head._eval_forward(mean, latent, std, actions, old_log_prob, advantages, clip_range, logp, sur, ratio, var)
         ctx.head, ctx.clip = head, clip_range
         ctx.save_for_backward(mean, latent, std, actions, var, ratio, advantages)
@@ -102,12 +107,10 @@ class _Evaluate(torch.autograd.Function):
         head = ctx.head
         mean, latent, std, actions, var, ratio, adv = ctx.saved_tensors
         B, L, A = mean.shape[0], head.latent_dim, head.act_dim
-        f4 = dict(dtype=torch.float32, device=head.device)
         need = ctx.needs_input_grad
-        g_logp = None if g_logp is None else g_logp.contiguous()
-        g_sur = None if g_sur is None else g_sur.contiguous()
-        g_mean, g_std = torch.empty((B, A), **f4), torch.empty((L, A), **f4)
-        g_lat = torch.empty((B, L), **f4) if need[2] else None
+        g_logp, g_sur = _contiguous(g_logp, g_sur)
+        g_mean, g_std = _fresh(head, (B, A), (L, A))
+        g_lat = _fresh(head, (B, L))[0] if need[2] else None
         head._eval_backward(mean, latent, std, actions, var, ratio, adv, ctx.clip, g_logp, g_sur, g_mean, g_lat, g_std)
         return None, g_mean if need[1] else None, g_lat, g_std if need[3] else None, None, None, None, None
 
@@ -153,8 +156,7 @@ class DeviceSDE:
         self._epoch = 0
         self._s = _lib.UsvSde(n, L, A, 0, seed, gid0, (ctypes.c_float * 4)(*lo), (ctypes.c_float * 4)(*hi))
         self._sp = ctypes.byref(self._s)
-        f4 = dict(dtype=torch.float32, device=device)
-        self._out = (torch.zeros((n, A), **f4), torch.zeros((n, A), **f4), torch.zeros((n,), **f4))
+        self._out = _fresh(self, (n, A), (n, A), (n,), make=torch.zeros)
         self._sq_out = self._scratch = None                # squashed's buffers, made by its first call
         self._eval_scratch = None                           # evaluate's backward scratch, grown with B
 
@@ -180,15 +182,12 @@ class DeviceSDE:
         float32 [N, L] with inner stride 1, a row stride that is a multiple of 4 and >= L, and a 16-B
         aligned base.  ``out``: three contiguous float32 tensors of those shapes to write instead."""
         n, L, A = self.n, self.latent_dim, self.act_dim
-        _lib.check_tensor("mean", mean, torch.float32, (n, A), self.device)
-        _lib.check_tensor("std", std, torch.float32, (L, A), self.device)
-        # a single env's row has no stride of its own: the kernel is then given L
-        stride = _lib.check_rows("latent", latent, torch.float32, (n, L), self.device, stride_multiple=4, align=16)
+        self._check(("mean", mean, (n, A)), ("std", std, (L, A)))
+        stride = self._latent_stride("latent", latent)
         if out is None:
             out = self._out
         else:
-            for name, t, s in zip(("out[0]", "out[1]", "out[2]"), out, ((n, A), (n, A), (n,))):
-                _lib.check_tensor(name, t, torch.float32, s, self.device)
+            self._check(*zip(("out[0]", "out[1]", "out[2]"), out, ((n, A), (n, A), (n,))))
         a, a_env, logp = out
         _lib.check(self.lib.usv_sde_sample(self._sp, self._epoch, _ptr(mean), _ptr(latent), stride, _ptr(std), _ptr(a),
                                            _ptr(a_env), _ptr(logp), _lib.stream_ptr(self.device)), self.lib)
@@ -200,23 +199,35 @@ class DeviceSDE:
         """SB3's ``exploration_mat`` of the current epoch for every env, [N, L, A]: a fresh tensor, or
         ``out``.  Off the hot path (``sample`` does not read it)."""
         n, L, A = self.n, self.latent_dim, self.act_dim
-        _lib.check_tensor("std", std, torch.float32, (L, A), self.device)
+        self._check(("std", std, (L, A)))
         if out is None:
-            out = torch.empty((n, L, A), dtype=torch.float32, device=self.device)
+            out, = _fresh(self, (n, L, A))
         else:
-            _lib.check_tensor("out", out, torch.float32, (n, L, A), self.device)
+            self._check(("out", out, (n, L, A)))
         _lib.check(self.lib.usv_sde_weights(self._sp, self._epoch, _ptr(std), _ptr(out),
                                             _lib.stream_ptr(self.device)), self.lib)
         return out
 
+    def _check(self, *table):
+        """``check_tensor`` for every (name, tensor, shape) of ``table`` whose tensor is not None."""
+        for name, t, shape in table:
+            if t is not None:
+                _lib.check_tensor(name, t, torch.float32, shape, self.device)
+
     def _latent_stride(self, name, t, n=None):
+        # a single env's row has no stride of its own: the kernel is then given L
         return _lib.check_rows(name, t, torch.float32, (self.n if n is None else n, self.latent_dim), self.device,
                                stride_multiple=4, align=16)
 
+    def _grown(self, attr, need):
+        """The scratch buffer ``attr`` of this head, made anew where it holds fewer than ``need`` floats."""
+        if getattr(self, attr) is None or getattr(self, attr).numel() < need:
+            setattr(self, attr, _fresh(self, (need,))[0])
+        return getattr(self, attr)
+
     def _squash_forward(self, mean, latent, std, out):
         n, L, A = self.n, self.latent_dim, self.act_dim
-        _lib.check_tensor("mean", mean, torch.float32, (n, A), self.device)
-        _lib.check_tensor("std", std, torch.float32, (L, A), self.device)
+        self._check(("mean", mean, (n, A)), ("std", std, (L, A)))
         stride = self._latent_stride("latent", latent)
         act, env, logp, gauss, var = out
         _lib.check(self.lib.usv_sde_squash_forward(self._sp, self._epoch, _ptr(mean), _ptr(latent), stride, _ptr(std),
@@ -225,17 +236,13 @@ class DeviceSDE:
 
     def _squash_backward(self, epoch, mean, latent, std, gauss, var, g_act, g_logp, g_mean, g_lat, g_std):
         n, L, A = self.n, self.latent_dim, self.act_dim
-        for name, t, shape in (("g_act", g_act, (n, A)), ("g_logp", g_logp, (n,)), ("g_mean", g_mean, (n, A)),
-                               ("g_std", g_std, (L, A)), ("gauss", gauss, (n, A)), ("var", var, (n, A))):
-            if t is not None:
-                _lib.check_tensor(name, t, torch.float32, shape, self.device)
-        if self._scratch is None:
-            self._scratch = torch.empty((self.lib.usv_sde_squash_scratch_floats(self._sp),), dtype=torch.float32,
-                                        device=self.device)
+        self._check(("g_act", g_act, (n, A)), ("g_logp", g_logp, (n,)), ("g_mean", g_mean, (n, A)),
+                    ("g_std", g_std, (L, A)), ("gauss", gauss, (n, A)), ("var", var, (n, A)))
+        scratch = self._grown("_scratch", self.lib.usv_sde_squash_scratch_floats(self._sp))
         _lib.check(self.lib.usv_sde_squash_backward(
             self._sp, epoch, _ptr(mean), _ptr(latent), self._latent_stride("latent", latent), _ptr(std), _ptr(gauss),
             _ptr(var), _ptr(g_act), _ptr(g_logp), _ptr(g_mean), _ptr(g_lat), self._latent_stride("g_lat", g_lat),
-            _ptr(g_std), _ptr(self._scratch), _lib.stream_ptr(self.device)), self.lib)
+            _ptr(g_std), _ptr(scratch), _lib.stream_ptr(self.device)), self.lib)
 
     def squashed(self, mean, latent, std):
         """SAC's head (``squash_output=True``, ``learn_features=True``): ``SquashedSample(actions, env_actions,
@@ -263,8 +270,7 @@ class DeviceSDE:
             return SquashedSample(*_Squashed.apply(self, mean, latent, std))
         if self._sq_out is None:
             n, A = self.n, self.act_dim
-            f4 = dict(dtype=torch.float32, device=self.device)
-            self._sq_out = tuple(torch.zeros(s, **f4) for s in ((n, A), (n, A), (n,), (n, A), (n, A)))
+            self._sq_out = _fresh(self, (n, A), (n, A), (n,), (n, A), (n, A), make=torch.zeros)
         self._squash_forward(mean.detach(), latent.detach(), std.detach(), self._sq_out)
         act, env, logp, gauss, _ = self._sq_out
         if self.copy:
@@ -273,12 +279,9 @@ class DeviceSDE:
 
     def _eval_forward(self, mean, latent, std, actions, old_log_prob, advantages, clip_range, logp, sur, ratio, var):
         B, L, A = mean.shape[0], self.latent_dim, self.act_dim
-        for name, t, shape in (("mean", mean, (B, A)), ("std", std, (L, A)), ("actions", actions, (B, A)),
-                               ("old_log_prob", old_log_prob, (B,)), ("advantages", advantages, (B,)),
-                               ("log_prob", logp, (B,)), ("surrogate", sur, (B,)), ("ratio", ratio, (B,)),
-                               ("var", var, (B, A))):
-            if t is not None:
-                _lib.check_tensor(name, t, torch.float32, shape, self.device)
+        self._check(("mean", mean, (B, A)), ("std", std, (L, A)), ("actions", actions, (B, A)),
+                    ("old_log_prob", old_log_prob, (B,)), ("advantages", advantages, (B,)), ("log_prob", logp, (B,)),
+                    ("surrogate", sur, (B,)), ("ratio", ratio, (B,)), ("var", var, (B, A)))
         _lib.check(self.lib.usv_sde_eval_forward(
             self._sp, B, _ptr(mean), _ptr(latent), self._latent_stride("latent", latent, B), _ptr(std), _ptr(actions),
             _ptr(old_log_prob), _ptr(advantages), 0.0 if clip_range is None else clip_range, _ptr(logp), _ptr(sur),
@@ -287,20 +290,15 @@ class DeviceSDE:
     def _eval_backward(self, mean, latent, std, actions, var, ratio, advantages, clip_range, g_logp, g_sur, g_mean, g_lat,
                        g_std):
         B, L, A = mean.shape[0], self.latent_dim, self.act_dim
-        for name, t, shape in (("mean", mean, (B, A)), ("std", std, (L, A)), ("actions", actions, (B, A)),
-                               ("var", var, (B, A)), ("ratio", ratio, (B,)), ("advantages", advantages, (B,)),
-                               ("g_logp", g_logp, (B,)), ("g_sur", g_sur, (B,)), ("g_mean", g_mean, (B, A)),
-                               ("g_std", g_std, (L, A))):
-            if t is not None:
-                _lib.check_tensor(name, t, torch.float32, shape, self.device)
-        need = self.lib.usv_sde_eval_scratch_floats(self._sp, B)
-        if self._eval_scratch is None or self._eval_scratch.numel() < need:
-            self._eval_scratch = torch.empty((need,), dtype=torch.float32, device=self.device)
+        self._check(("mean", mean, (B, A)), ("std", std, (L, A)), ("actions", actions, (B, A)), ("var", var, (B, A)),
+                    ("ratio", ratio, (B,)), ("advantages", advantages, (B,)), ("g_logp", g_logp, (B,)),
+                    ("g_sur", g_sur, (B,)), ("g_mean", g_mean, (B, A)), ("g_std", g_std, (L, A)))
+        scratch = self._grown("_eval_scratch", self.lib.usv_sde_eval_scratch_floats(self._sp, B))
         _lib.check(self.lib.usv_sde_eval_backward(
             self._sp, B, _ptr(mean), _ptr(latent), self._latent_stride("latent", latent, B), _ptr(std), _ptr(actions),
             _ptr(var), _ptr(ratio), _ptr(advantages), 0.0 if clip_range is None else clip_range, _ptr(g_logp), _ptr(g_sur),
             _ptr(g_mean), _ptr(g_lat), 0 if g_lat is None else self._latent_stride("g_lat", g_lat, B), _ptr(g_std),
-            _ptr(self._eval_scratch), _lib.stream_ptr(self.device)), self.lib)
+            _ptr(scratch), _lib.stream_ptr(self.device)), self.lib)
 
     def evaluate(self, mean, latent, std, actions, old_log_prob=None, advantages=None, clip_range=None):
         """PPO's update-time head, SB3's ``evaluate_actions`` for gSDE with the clipped surrogate on the same row:
@@ -336,8 +334,7 @@ class DeviceSDE:
         if torch.is_grad_enabled() and (mean.requires_grad or latent.requires_grad or std.requires_grad):
             return Evaluation(*_Evaluate.apply(self, mean, latent, std, *data, clip_range))
         B = mean.shape[0]
-        f4 = dict(dtype=torch.float32, device=self.device)
-        logp = torch.empty((B,), **f4)
-        sur, ratio = (torch.empty((B,), **f4), torch.empty((B,), **f4)) if all(given) else (None, None)
+        logp, = _fresh(self, (B,))
+        sur, ratio = _fresh(self, (B,), (B,)) if all(given) else (None, None)
         self._eval_forward(mean.detach(), latent.detach(), std.detach(), *data, clip_range, logp, sur, ratio, None)
         return Evaluation(logp, sur, ratio)

@@ -15,13 +15,13 @@ under 4x the maximum this program measured, MEASURED below: 4x is this head's ma
 Measured maxima of the host replay over SHAPES (x86-64, glibc):
     var 1.67e-07  logp 9.77e-08  ratio 6.17e-08  sur 6.54e-08  g_mean 1.74e-07  g_lat 2.54e-07  g_std 1.77e-07"""
 import ctypes
-import subprocess
 
 import numpy as np
 import pytest
 
 import sde_eval_ref as E
 import sde_squash_ref as Q
+from sde_host import bits, compile_replay, load_lib, make_sde, run_replay
 
 MEASURED = {"var": 1.67e-7, "logp": 9.77e-8, "ratio": 6.17e-8, "sur": 6.54e-8, "g_mean": 1.74e-7, "g_lat": 2.54e-7,
             "g_std": 1.77e-7}                             # the host replay's maxima over SHAPES (rounded up)
@@ -112,42 +112,22 @@ int main(int argc, char** argv) {
 
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
-    """The replay program, plain (-O3 for a target with FMA, where the compiler would contract) and with
-    AddressSanitizer + UBSan (both stand-alone host binaries)."""
-    import platform
-    from gym_usv_amd.build import CSRC, hipcc
-    d = tmp_path_factory.mktemp("sde_eval_math")
-    src = d / "replay.cpp"
-    src.write_text(MAIN)
-    fma = ["-mfma"] if platform.machine() in ("x86_64", "AMD64") else []
-    out = {}
-    for name, flags in (("plain", ["-O3", *fma]),
-                        ("san", ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"])):
-        exe = d / f"replay_{name}"
-        subprocess.run([hipcc(), "-x", "c++", "-std=c++17", "-Wall", *flags, f"-I{CSRC}", "-o", str(exe), str(src)],
-                       check=True)
-        out[name] = str(exe)
-    return out
+    return compile_replay(tmp_path_factory.mktemp("sde_eval_math"), MAIN)
+
+
+@pytest.fixture(scope="module")
+def squash_programs(tmp_path_factory):
+    """The replay of the sample and squashed heads (tests/test_sde_squash_math.py)."""
+    from test_sde_squash_math import MAIN as SQUASH_MAIN
+    return compile_replay(tmp_path_factory.mktemp("sde_squash_for_eval"), SQUASH_MAIN, variants=("plain",))
 
 
 def replay(exe, n, L, A, case_inputs, clip=E.CLIP, ppo=True, with_g_lat=True):
-    data = b"".join(np.ascontiguousarray(x, np.float32).tobytes() for x in case_inputs)
-    p = subprocess.run([exe, "eval", str(n), str(L), str(A), repr(float(clip)), str(int(ppo)), str(int(with_g_lat))],
-                       input=data, capture_output=True, timeout=120)
-    assert p.returncode == 0, (p.returncode, p.stderr.decode(errors="replace")[-2000:])
-    o, at, out = p.stdout, 0, {}
-    for name, shape in (("var", (n, A)), ("logp", (n,)), ("ratio", (n,)), ("sur", (n,)), ("t", (n,)), ("g_mean", (n, A)),
-                        ("g_lat", (n, L)), ("g_std", (L, A)), ("var_sample", (n, A))):
-        cnt = int(np.prod(shape))
-        out[name] = np.frombuffer(o, np.float32, cnt, at).reshape(shape)
-        at += 4 * cnt
-    assert at == len(o)
-    out["R"], out["P"] = (int(x) for x in p.stderr.decode().split("C ", 1)[1].split())
+    fields = (("var", (n, A)), ("logp", (n,)), ("ratio", (n,)), ("sur", (n,)), ("t", (n,)), ("g_mean", (n, A)),
+              ("g_lat", (n, L)), ("g_std", (L, A)), ("var_sample", (n, A)))
+    out, (out["R"], out["P"]) = run_replay(exe, ("eval", n, L, A, repr(float(clip)), int(ppo), int(with_g_lat)),
+                                           case_inputs, [(name, np.float32, shape) for name, shape in fields])
     return out
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("n,L,A", E.SHAPES, ids=lambda v: str(v))
@@ -169,24 +149,15 @@ def test_replay_against_the_float64_reference(programs, n, L, A):
 
 
 @pytest.mark.parametrize("n,L,A", Q.SHAPES, ids=lambda v: str(v))
-def test_var_is_the_sample_heads_bit_for_bit(programs, n, L, A):
+def test_var_is_the_sample_heads_bit_for_bit(programs, squash_programs, n, L, A):
     """Against the variance of the sample head's own accumulation (sde_accum) in this program, and against the
     existing replay of the sample and squashed heads (tests/test_sde_squash_math.py) on that test's inputs."""
-    from test_sde_squash_math import MAIN as SQUASH_MAIN
     from test_sde_squash_math import replay as squash_replay
-    from gym_usv_amd.build import CSRC, hipcc
-    import os
-    import tempfile
     inp = E.inputs(n, L, A)
     got = replay(programs["plain"], n, L, A, inp)
     assert (bits(got["var"]) == bits(got["var_sample"])).all()
     mean, lat, std, ga, gl = Q.inputs(n, L, A)
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "squash.cpp"), os.path.join(d, "squash")
-        with open(src, "w") as f:
-            f.write(SQUASH_MAIN)
-        subprocess.run([hipcc(), "-x", "c++", "-std=c++17", "-O1", f"-I{CSRC}", "-o", exe, src], check=True)
-        want = squash_replay(exe, n, L, A, (mean, lat, std, ga, gl))
+    want = squash_replay(squash_programs["plain"], n, L, A, (mean, lat, std, ga, gl))
     z = np.zeros(n, np.float32)
     mine = replay(programs["plain"], n, L, A, (mean, lat, std, want["gauss"], z, z, z, z), ppo=False)
     assert (bits(mine["var"]) == bits(want["var"])).all()
@@ -261,17 +232,7 @@ def test_replay_under_sanitizers(programs):
 
 @pytest.fixture(scope="module")
 def lib():
-    from gym_usv_amd import _lib
-    from gym_usv_amd.build import build_library
-    build_library(verbose=False)
-    return _lib.load()
-
-
-def make_sde(**kw):
-    from gym_usv_amd import _lib
-    f = dict(n=4, latent_dim=8, act_dim=2, reserved=0, seed=1, gid0=0)
-    f.update(kw)
-    return _lib.UsvSde(low=(ctypes.c_float * 4)(0.0, -1.0, 0.0, 0.0), high=(ctypes.c_float * 4)(1.0, 1.0, 0.0, 0.0), **f)
+    return load_lib()
 
 
 def test_eval_calls_refuse_bad_arguments_without_gpu(lib):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import sde_ref as R
+from sde_host import bits, compile_replay, load_lib, make_sde, run_replay
 
 KAT = (((0, 0, 0, 0), (0, 0), "6627e8d5 e169c58d bc57ac4c 9b00dbd8"),
        ((0xFFFFFFFF,) * 4, (0xFFFFFFFF,) * 2, "408f276d 41c83b0e a20bc7c6 6d5451fd"),
@@ -111,22 +112,7 @@ int main(int argc, char** argv) {
 
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
-    """The replay program, plain (-O3 for a target with FMA, where the compiler would contract) and with
-    AddressSanitizer + UBSan (both stand-alone host binaries)."""
-    import platform
-    from gym_usv_amd.build import CSRC, hipcc
-    d = tmp_path_factory.mktemp("sde_math")
-    src = d / "replay.cpp"
-    src.write_text(MAIN)
-    fma = ["-mfma"] if platform.machine() in ("x86_64", "AMD64") else []
-    out = {}
-    for name, flags in (("plain", ["-O3", *fma]),
-                        ("san", ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"])):
-        exe = d / f"replay_{name}"
-        subprocess.run([hipcc(), "-x", "c++", "-std=c++17", "-Wall", *flags, f"-I{CSRC}", "-o", str(exe), str(src)],
-                       check=True)
-        out[name] = str(exe)
-    return out
+    return compile_replay(tmp_path_factory.mktemp("sde_math"), MAIN)
 
 
 def inputs(n, L, A, seed=0):
@@ -144,25 +130,11 @@ LOW, HIGH = (0.0, -1.0), (1.0, 1.0)
 
 
 def head(exe, n, L, A, seed, gid0, epoch, mean, lat, std, low=LOW, high=HIGH):
-    data = b"".join(np.ascontiguousarray(x, np.float32).tobytes() for x in (mean, lat, std))
-    p = subprocess.run([exe, "head", str(n), str(L), str(A), str(seed), str(gid0), str(epoch),
-                        *(repr(float(x)) for x in (*low, *high))], input=data, capture_output=True, timeout=120)
-    assert p.returncode == 0, (p.returncode, p.stderr.decode(errors="replace")[-2000:])
-    o, B, at = p.stdout, L * A // 4, 0
-    out = {}
-    for name, dt, shape in (("num", np.uint32, (n, L, A, 2)), ("words", np.uint32, (n, B, 8)),
-                            ("w", np.float32, (n, L, A)), ("act", np.float32, (n, A)),
-                            ("env", np.float32, (n, A)), ("logp", np.float32, (n,))):
-        cnt = int(np.prod(shape))
-        out[name] = np.frombuffer(o, dt, cnt, at).reshape(shape)
-        at += 4 * cnt
-    assert at == len(o)
-    out["consts"] = [int(x) for x in p.stderr.decode().split("C ", 1)[1].split()]
+    out, out["consts"] = run_replay(
+        exe, ("head", n, L, A, seed, gid0, epoch, *(repr(float(x)) for x in (*low, *high))), (mean, lat, std),
+        (("num", np.uint32, (n, L, A, 2)), ("words", np.uint32, (n, L * A // 4, 8)), ("w", np.float32, (n, L, A)),
+         ("act", np.float32, (n, A)), ("env", np.float32, (n, A)), ("logp", np.float32, (n,))))
     return out
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def test_philox_known_answers(programs):
@@ -277,10 +249,7 @@ def test_reference_distribution():
 
 @pytest.fixture(scope="module")
 def lib():
-    from gym_usv_amd import _lib
-    from gym_usv_amd.build import build_library
-    build_library(verbose=False)
-    return _lib.load()
+    return load_lib()
 
 
 def test_sde_calls_refuse_bad_arguments_without_gpu(lib):
@@ -290,11 +259,6 @@ def test_sde_calls_refuse_bad_arguments_without_gpu(lib):
     buf = (ctypes.c_uint8 * 256)()
     p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 16
     nan = float("nan")
-
-    def sde(low=(0.0, -1.0, 0.0, 0.0), high=(1.0, 1.0, 0.0, 0.0), **kw):
-        f = dict(n=4, latent_dim=8, act_dim=2, reserved=0, seed=1, gid0=0)
-        f.update(kw)
-        return _lib.UsvSde(low=(ctypes.c_float * 4)(*low), high=(ctypes.c_float * 4)(*high), **f)
 
     def calls(s, word, stride=8, which=(0, 1), mean=p, lat=p, std=p, act=p, env=p, logp=p, w=p):
         sp = ctypes.byref(s) if s is not None else None
@@ -310,21 +274,21 @@ def test_sde_calls_refuse_bad_arguments_without_gpu(lib):
                      (dict(latent_dim=4100), b"latent_dim"), (dict(latent_dim=-4), b"latent_dim"),
                      (dict(reserved=1), b"reserved"), (dict(low=(2.0, -1.0, 0, 0)), b"low must be <= high"),
                      (dict(low=(0.0, nan, 0, 0)), b"low must be <= high"), (dict(high=(nan, 1.0, 0, 0)), b"low must be <= high")):
-        calls(sde(**kw), word)
+        calls(make_sde(**kw), word)
     # bounds past act_dim are not looked at: the next refusal is the buffers'
-    calls(sde(act_dim=1, low=(0.0, 5.0, 0, 0)), b"null buffer", std=None)
-    calls(sde(), b"row stride", stride=7, which=(0,))
-    calls(sde(), b"row stride", stride=10, which=(0,))
-    calls(sde(), b"row stride", stride=4, which=(0,))
+    calls(make_sde(act_dim=1, low=(0.0, 5.0, 0, 0)), b"null buffer", std=None)
+    calls(make_sde(), b"row stride", stride=7, which=(0,))
+    calls(make_sde(), b"row stride", stride=10, which=(0,))
+    calls(make_sde(), b"row stride", stride=4, which=(0,))
     for name in ("mean", "lat", "std", "act", "env", "logp"):
-        calls(sde(), b"null buffer", which=(0,), **{name: None})
-        calls(sde(), b"aligned", which=(0,), **{name: p + 2})
-    calls(sde(), b"aligned", which=(0,), lat=p + 4)         # 4-B aligned is not enough for the latent rows
-    calls(sde(), b"aligned", which=(0,), lat=p + 8)
+        calls(make_sde(), b"null buffer", which=(0,), **{name: None})
+        calls(make_sde(), b"aligned", which=(0,), **{name: p + 2})
+    calls(make_sde(), b"aligned", which=(0,), lat=p + 4)         # 4-B aligned is not enough for the latent rows
+    calls(make_sde(), b"aligned", which=(0,), lat=p + 8)
     for name in ("std", "w"):
-        calls(sde(), b"null buffer", which=(1,), **{name: None})
-        calls(sde(), b"aligned", which=(1,), **{name: p + 1})
-    calls(sde(n=2 ** 31 - 1, latent_dim=4096), b"blocks of 256", which=(1,))
+        calls(make_sde(), b"null buffer", which=(1,), **{name: None})
+        calls(make_sde(), b"aligned", which=(1,), **{name: p + 1})
+    calls(make_sde(n=2 ** 31 - 1, latent_dim=4096), b"blocks of 256", which=(1,))
     assert ctypes.sizeof(_lib.UsvSde) == 4 * 4 + 2 * 8 + 8 * 4
 
 

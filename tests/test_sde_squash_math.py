@@ -16,12 +16,12 @@ Measured maxima of the host replay over SHAPES (x86-64, glibc):
 The gradient errors are taken at the program's own normals, which "z" bounds against sde_ref.normals as the
 existing head's test does; why, and the figures at the reference's normals, are in sde_squash_ref.py's docstring."""
 import ctypes
-import subprocess
 
 import numpy as np
 import pytest
 
 import sde_squash_ref as Q
+from sde_host import bits, compile_replay, load_lib, make_sde, run_replay
 
 MEASURED = {"z": 4.14e-7, "u": 4.26e-7, "a": 8.75e-8, "var": 1.68e-7, "logp": 9.07e-8, "g_mean": 1.47e-7,
             "g_lat": 1.86e-7, "g_std": 9.66e-8}         # the host replay's maxima over SHAPES (rounded up)
@@ -128,42 +128,16 @@ int main(int argc, char** argv) {
 
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
-    """The replay program, plain (-O3 for a target with FMA, where the compiler would contract) and with
-    AddressSanitizer + UBSan (both stand-alone host binaries)."""
-    import platform
-    from gym_usv_amd.build import CSRC, hipcc
-    d = tmp_path_factory.mktemp("sde_squash_math")
-    src = d / "replay.cpp"
-    src.write_text(MAIN)
-    fma = ["-mfma"] if platform.machine() in ("x86_64", "AMD64") else []
-    out = {}
-    for name, flags in (("plain", ["-O3", *fma]),
-                        ("san", ["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"])):
-        exe = d / f"replay_{name}"
-        subprocess.run([hipcc(), "-x", "c++", "-std=c++17", "-Wall", *flags, f"-I{CSRC}", "-o", str(exe), str(src)],
-                       check=True)
-        out[name] = str(exe)
-    return out
+    return compile_replay(tmp_path_factory.mktemp("sde_squash_math"), MAIN)
 
 
 def replay(exe, n, L, A, case_inputs, seed=Q.SEED, gid0=Q.GID0, epoch=Q.EPOCH, low=Q.LOW, high=Q.HIGH):
-    data = b"".join(np.ascontiguousarray(x, np.float32).tobytes() for x in case_inputs)
-    p = subprocess.run([exe, "squash", str(n), str(L), str(A), str(seed), str(gid0), str(epoch),
-                        *(repr(float(x)) for x in (*low, *high))], input=data, capture_output=True, timeout=120)
-    assert p.returncode == 0, (p.returncode, p.stderr.decode(errors="replace")[-2000:])
-    o, at, out = p.stdout, 0, {}
-    for name, shape in (("act", (n, A)), ("env", (n, A)), ("gauss", (n, A)), ("var", (n, A)), ("logp", (n,)),
-                        ("g_mean", (n, A)), ("g_lat", (n, L)), ("g_std", (L, A)), ("z", (n, L, A))):
-        cnt = int(np.prod(shape))
-        out[name] = np.frombuffer(o, np.float32, cnt, at).reshape(shape)
-        at += 4 * cnt
-    assert at == len(o)
-    out["R"], out["P"] = (int(x) for x in p.stderr.decode().split("C ", 1)[1].split())
+    fields = (("act", (n, A)), ("env", (n, A)), ("gauss", (n, A)), ("var", (n, A)), ("logp", (n,)), ("g_mean", (n, A)),
+              ("g_lat", (n, L)), ("g_std", (L, A)), ("z", (n, L, A)))
+    out, (out["R"], out["P"]) = run_replay(
+        exe, ("squash", n, L, A, seed, gid0, epoch, *(repr(float(x)) for x in (*low, *high))), case_inputs,
+        [(name, np.float32, shape) for name, shape in fields])
     return out
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("n,L,A", Q.SHAPES, ids=lambda v: str(v))
@@ -219,18 +193,7 @@ def test_replay_under_sanitizers(programs):
 
 @pytest.fixture(scope="module")
 def lib():
-    from gym_usv_amd import _lib
-    from gym_usv_amd.build import build_library
-    build_library(verbose=False)
-    return _lib.load()
-
-
-def make_sde(**kw):
-    from gym_usv_amd import _lib
-    f = dict(n=4, latent_dim=8, act_dim=2, reserved=0, seed=1, gid0=0)
-    low, high = kw.pop("low", (0.0, -1.0, 0.0, 0.0)), kw.pop("high", (1.0, 1.0, 0.0, 0.0))
-    f.update(kw)
-    return _lib.UsvSde(low=(ctypes.c_float * 4)(*low), high=(ctypes.c_float * 4)(*high), **f)
+    return load_lib()
 
 
 def test_squash_calls_refuse_bad_arguments_without_gpu(lib):
