@@ -14,9 +14,14 @@ is a compact SAC with config_sac's hyper-parameters where they carry over:
   and of next_obs per transition where full storage keeps two 715-float stacks, and one launch per
   minibatch that rebuilds both windows (``sample`` = one device ``randint`` + ``gather``);
   ``device_replay=False``: a torch full-storage buffer (two ``[R, N, W]`` tensors, row copies to store,
-  five indexed reads to sample);
+  indexed reads to sample);
 * ``check_replay=True`` keeps both and asserts that every minibatch of the two is bitwise equal (the
-  assertion reads one flag per minibatch back to the host: a test mode).
+  assertion reads one flag per minibatch back to the host: a test mode);
+* ``n_steps=N`` (``--n-steps N``): SB3 2.7's n-step returns.  A minibatch is ``gather_nstep``'s: the
+  discounted sum of up to ``N`` rewards, the ``next_observations`` and ``dones`` at the end of that run and a
+  per-sample ``discounts``, and the target is ``rewards + (1 - dones) * discounts * q_next``.  With the
+  default 1 that is the one-step target (``discounts`` is ``float32(gamma)`` everywhere).  The torch buffer
+  computes the same with three indexed reads per step of the run and six more per minibatch.
 
 * ``sde_kernel=True`` (``--sde-kernel``): config_sac's ``use_sde=True``, ``sde_sample_freq=4``,
   ``log_std_init=-3`` through ``gym_usv_amd.DeviceSDE.squashed`` (one HIP launch forward, two backward, no
@@ -54,6 +59,7 @@ import torch.nn.functional as F  # noqa: E402
 
 CONFIG_SAC = {"n_stack": 5, "net_arch": (400, 300), "lr": 1e-4, "gamma": 0.99, "tau": 0.005, "buffer_size": 400000,
               "batch_size": 256, "train_freq": 8, "gradient_steps": 8, "learning_starts": 12,
+              "n_steps": 1,                                         # SB3 2.7's n_steps (config_sac has none: 1)
               "sde_sample_freq": 4, "log_std_init": -3.0}             # the last two: sde_kernel=True only
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0   # SB3 sac/policies.py
 CLIP_MEAN = 2.0                         # SB3 sac/policies.py, with use_sde
@@ -113,7 +119,7 @@ class TorchReplay:
         R = self.rows
         self.obs, self.next_obs, self.act = z(R, n, W), z(R, n, W), z(R, n, A)
         self.rew, self.done, self.timeout = z(R, n), z(R, n), z(R, n)
-        self.count = 0
+        self.count, self._tables = 0, {}
 
     @property
     def size(self):
@@ -138,10 +144,37 @@ class TorchReplay:
         return ReplaySamples(self.obs.reshape(-1, W)[idx], self.act.reshape(-1, A)[idx], self.next_obs.reshape(-1, W)[idx],
                              dones, self.rew.reshape(-1)[idx].reshape(-1, 1))
 
+    def gather_nstep(self, idx, n_steps, table):
+        """SB3's ``NStepReplayBuffer._get_samples`` as ``DeviceReplay.gather_nstep`` defines it: ``table`` is
+        its ``discount_table(gamma, n_steps)``, the return the float32 sum in the order of the steps (one
+        multiply and one add per step: eager torch fuses neither), a run of one step the stored reward."""
+        from gym_usv_amd.replay import NStepReplaySamples
+        n, R, W, A = self.n, self.rows, self.obs.shape[-1], self.act.shape[-1]
+        slot, e = idx // n, idx % n
+        last = (self.count - 1) % R
+        rew, done, timeout = self.rew.reshape(-1), self.done.reshape(-1), self.timeout.reshape(-1)
+        is_open = torch.ones_like(idx, dtype=torch.bool)
+        ret, end = torch.zeros_like(idx, dtype=torch.float32), idx.clone()      # `end`: the run's last transition
+        m = torch.zeros_like(idx)
+        for j in range(n_steps):
+            s = (slot + j) % R
+            f = s * n + e
+            ret = torch.where(is_open, rew[f] if j == 0 else ret + rew[f] * table[j], ret)
+            end, m = torch.where(is_open, f, end), torch.where(is_open, j, m)
+            is_open = is_open & (done[f] == 0) & (timeout[f] == 0) & (s != last)
+        dones = (done[end] * (1 - timeout[end])).reshape(-1, 1)
+        key = tuple(table)
+        if key not in self._tables:                         # uploaded once per table
+            self._tables[key] = torch.tensor(table, dtype=torch.float32, device=idx.device)
+        discounts = self._tables[key][m + 1].reshape(-1, 1)
+        return NStepReplaySamples(self.obs.reshape(-1, W)[idx], self.act.reshape(-1, A)[idx],
+                                  self.next_obs.reshape(-1, W)[end], dones, ret.reshape(-1, 1), discounts)
+
 
 class SAC:
     def __init__(self, env, seed=0, device_replay=True, check_replay=False, sde_kernel=False, **cfg):
         from gym_usv_amd import DeviceReplay, DeviceSDE
+        from gym_usv_amd.replay import discount_table
         from gym_usv_amd.wrappers import DeviceWrappers
         self.cfg = c = dict(CONFIG_SAC, **cfg)
         self.env, self.device = env, env.device
@@ -168,10 +201,12 @@ class SAC:
         self.wr = DeviceWrappers(self.N, D, k, d, env.reward.dtype)
         self.rb = self.shadow = None
         if device_replay or check_replay:
-            self.rb = DeviceReplay(self.N, c["buffer_size"], W, A, d, env.reward.dtype, n_stack=k)
+            self.rb = DeviceReplay(self.N, c["buffer_size"], W, A, d, env.reward.dtype, n_stack=k, n_steps=c["n_steps"],
+                                   gamma=c["gamma"])
         if not device_replay or check_replay:
             self.shadow = TorchReplay(self.N, c["buffer_size"], W, A, d)
         self.device_replay = device_replay
+        self.table = discount_table(c["gamma"], c["n_steps"])
         obs, _ = env.reset(seed=seed)
         self.wr.reset(obs)
         self.env_steps = self.checked = 0
@@ -208,9 +243,10 @@ class SAC:
         c = self.cfg
         size = self.rb.size if self.rb is not None else self.shadow.size
         idx = torch.randint(0, size * self.N, (c["batch_size"],), device=self.device)
-        mb = self.rb.gather(idx) if self.device_replay else self.shadow.gather(idx)
+        legs = (lambda: self.rb.gather_nstep(idx), lambda: self.shadow.gather_nstep(idx, c["n_steps"], self.table))
+        mb = legs[0 if self.device_replay else 1]()
         if self.rb is not None and self.shadow is not None:
-            other = self.shadow.gather(idx) if self.device_replay else self.rb.gather(idx)
+            other = legs[1 if self.device_replay else 0]()
             for name, x, y in zip(mb._fields, mb, other):
                 assert x.shape == y.shape and torch.equal(x.contiguous().view(torch.int32), y.contiguous().view(torch.int32)), \
                     f"minibatch field {name} differs between DeviceReplay and the torch buffer"
@@ -239,7 +275,7 @@ class SAC:
             with torch.no_grad():
                 a2, logp2 = self.policy(mb.next_observations)
                 q_next = torch.min(*self.target(mb.next_observations, a2)) - ent * logp2[:, None]
-                target = mb.rewards + (1 - mb.dones) * c["gamma"] * q_next
+                target = mb.rewards + (1 - mb.dones) * mb.discounts * q_next
             q1, q2 = self.critic(mb.observations, mb.actions)
             critic_loss = 0.5 * (F.mse_loss(q1, target) + F.mse_loss(q2, target))
             self.opt_c.zero_grad(set_to_none=True)
@@ -308,9 +344,11 @@ def main():
     ap.add_argument("--device-replay", action="store_true", help="DeviceReplay instead of the torch full-storage buffer")
     ap.add_argument("--check-replay", action="store_true", help="keep both buffers and compare every minibatch bitwise")
     ap.add_argument("--sde-kernel", action="store_true", help="gSDE (config_sac's use_sde) through DeviceSDE.squashed")
+    ap.add_argument("--n-steps", type=int, default=CONFIG_SAC["n_steps"],
+                    help="n-step returns (SB3 2.7's n_steps) through sample_nstep; 1: the one-step target")
     a = ap.parse_args()
     train(a.env_id, a.envs, a.steps, a.seed, device_replay=a.device_replay, check_replay=a.check_replay,
-          sde_kernel=a.sde_kernel, buffer_size=a.buffer_size, batch_size=a.batch_size)
+          sde_kernel=a.sde_kernel, buffer_size=a.buffer_size, batch_size=a.batch_size, n_steps=a.n_steps)
 
 
 if __name__ == "__main__":

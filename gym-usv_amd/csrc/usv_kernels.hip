@@ -27,8 +27,9 @@
 //   usv_sde.hpp           gSDE heads: one row loop under the three forwards, the two backwards, weights
 //                         (usv_sde_sample / usv_sde_weights / usv_sde_squash_forward / _backward / usv_sde_eval_forward /
 //                         _backward)
-//   usv_replay_math.hpp   replay buffer: slots, frame rows, age and live masks (host C++, no HIP)
-//   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather)
+//   usv_replay_math.hpp   replay buffer: slots, frame rows, age and live masks, n-step runs (host C++, no HIP)
+//   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather /
+//                         _gather_nstep)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -1507,6 +1508,38 @@ int usv_replay_gather(const usv_replay* rp, int64_t count, const int64_t* idx, i
   const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
   hipLaunchKernelGGL(replay_gather_kernel, grid, block, 0, (hipStream_t)stream, a, rp_laps(count, a.R, a.k),
                      (long long)rp_size(count, a.R), idx, (int)B, obs_out, act_out, next_obs_out, done_out, rew_out);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_replay_gather_nstep(const usv_replay* rp, int64_t count, const int64_t* idx, int32_t B, int32_t n_steps,
+                            const float* table, float* obs_out, float* act_out, float* next_obs_out, float* done_out,
+                            float* rew_out, float* discount_out, void* stream) {
+  RpArgs a;
+  int dev;
+  if (count < 0) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: count must be >= 0");
+  if (B <= 0) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: B must be > 0");
+  if (n_steps < 1 || n_steps > kRpMaxNStep) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: n_steps must be in [1, 32]");
+  if (!table) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: null discount table");
+  RpDiscounts tab = {};
+  for (int j = 0; j <= n_steps; ++j) {
+    if (!std::isfinite(table[j])) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: a discount table entry is not finite");
+    tab.g[j] = table[j];
+  }
+  if (!idx) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: null idx");
+  const Bufs more = {{idx, 8},      {obs_out, 4}, {act_out, 4},     {next_obs_out, 4},
+                     {done_out, 4}, {rew_out, 4}, {discount_out, 4}};
+  const BufFault of = check_bufs(more.begin() + 1, 6);  // the outputs
+  if (of == kBufNull) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: null output");
+  if ((reinterpret_cast<uintptr_t>(idx) & 7) != 0) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: idx is not 8-B aligned");
+  if (of == kBufAlign) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: an output is not 4-B aligned");
+  if (int rc = replay_args(rp, more, a, dev)) return rc;
+  DeviceGuard g(dev);
+  const int per_block = kWaves * kRpRows;
+  const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
+  hipLaunchKernelGGL(replay_gather_nstep_kernel, grid, block, 0, (hipStream_t)stream, a, rp_laps(count, a.R, a.k),
+                     (long long)rp_size(count, a.R), idx, (int)B, (int)n_steps, tab, obs_out, act_out, next_obs_out,
+                     done_out, rew_out, discount_out);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

@@ -115,4 +115,49 @@ USV_RO_HD float rp_done_out(uint8_t done, uint8_t timeout) { return (float)done 
 USV_RO_HD int32_t rp_pieces(int32_t D) { return (D + 3) / 4; }
 USV_RO_HD int32_t rp_piece_col(int32_t piece, int32_t D) { return 4 * piece < D - 4 ? 4 * piece : D - 4; }
 
+// ---- n-step sampling (SB3 2.7's NStepReplayBuffer._get_samples; tests/replay_nstep_ref.py restates it)
+// The run of sample (slot, e) walks s_j = (slot + j) mod R for j = 0 .. n_steps - 1 and ends at m, the first
+// j with done[s_j], timeout[s_j] or s_j == last (SB3's temporary timeouts[pos - 1] |= ~dones[pos - 1]: a
+// run never crosses the write position of a full ring, nor enters the unwritten rows of a partly filled
+// one), else at n_steps - 1.  rewards = rew[s_0] for m == 0, else the float32 sum in the order j = 0 .. m of
+// fl(rew[s_j] g[j]), every product and sum rounded on its own; discounts = g[m + 1]; dones and next_obs are
+// those of transition (s_m, e).  g[j] = float32(double(gamma) ** j), j = 0 .. n_steps, is the caller's.
+constexpr int kRpMaxNStep = 32;
+
+USV_RO_HD int32_t rp_next_slot(int32_t s, int32_t R) { return s + 1 >= R ? 0 : s + 1; }
+USV_RO_HD bool rp_run_ends(uint8_t done, uint8_t timeout, int32_t s, int32_t last) {
+  return done != 0 || timeout != 0 || s == last;
+}
+// acc + fl(rew * g): two roundings, never one fused multiply-add.
+USV_RO_HD float rp_return_add(float acc, float rew, float g) {
+#pragma clang fp contract(off)
+  const float term = rew * g;
+  return acc + term;
+}
+
+struct RpRun {
+  int32_t m, slot;                     // the stop index and s_m
+  float ret;                           // the return so far
+  uint8_t done, timeout, age;          // of (s_m, e)
+  bool open;                           // no step has ended the run yet
+};
+USV_RO_HD RpRun rp_run_begin() { return RpRun{0, 0, 0.0f, 0, 0, 0, true}; }
+// Step j of the walk, at slot s, with what transition (s, e) stores; a step behind the stop changes nothing,
+// so the caller may load every step's values before it applies any.
+USV_RO_HD void rp_run_step(RpRun& r, int32_t j, int32_t s, uint8_t done, uint8_t timeout, uint8_t age, float rew,
+                           float gj, int32_t last) {
+  if (!r.open) return;
+  r.m = j;
+  r.slot = s;
+  r.done = done;
+  r.timeout = timeout;
+  r.age = age;
+  r.ret = j == 0 ? rew : rp_return_add(r.ret, rew, gj);
+  r.open = !rp_run_ends(done, timeout, s, last);
+}
+// Frame row j = 0 .. k - 2 of the next_obs window of transition c + m (steps c + m - k + 2 .. c + m), `first`
+// being the first row of the obs window of c: first + m + 1 + j <= (P - 1) + (R - 1) + 1 + (k - 2) < 2 P.
+// Slot k - 1 of that window is next_frame[s_m]; its liveness is rp_next_live_mask(age[s_m], k).
+USV_RO_HD int32_t rp_nstep_row(int32_t first, int32_t m, int32_t j, int32_t P) { return rp_wrap(first + m + 1 + j, P); }
+
 }  // namespace usv

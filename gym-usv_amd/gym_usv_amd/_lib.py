@@ -186,6 +186,8 @@ SIGNATURES = [
     ("usv_replay_put_obs", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _sz, _vp, _vp]),
     ("usv_replay_put_step", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _sz, _vp, _vp]),
     ("usv_replay_gather", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_replay_gather_nstep", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp]),
 ]
 
 _LIBS = {}

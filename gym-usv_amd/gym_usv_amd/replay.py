@@ -24,6 +24,11 @@ The stacked windows are not stored: the ring keeps the newest ``D`` columns of `
 slots of the window were live, and ``gather`` rebuilds both windows from the same ``k + 1`` frames, bit
 for bit what full storage would hold (tests/replay_ref.py).
 
+``DeviceReplay(..., n_steps=3, gamma=0.99)`` and ``rb.sample_nstep(256)`` are SB3 2.7's
+``NStepReplayBuffer``: the discounted sum of up to ``n_steps`` rewards, the ``next_observations`` and
+``dones`` at the end of that run and a per-sample ``discounts``, in the same single launch
+(``gather_nstep``; tests/replay_nstep_ref.py).  Nothing stored changes.
+
 The buffer stores what it is given: with ``DeviceWrappers(normalize={})`` that is the frame as normalised
 at collection time.  Re-normalising stored observations with later statistics (SB3's
 ``_normalize_obs(..., env)`` in ``_get_samples``) is not done.
@@ -42,6 +47,15 @@ from ._lib import ptr as _ptr
 # The fields of SB3's ReplayBufferSamples (common/type_aliases.py), in its order.
 ReplaySamples = collections.namedtuple(
     "ReplaySamples", ("observations", "actions", "next_observations", "dones", "rewards"))
+# ... and of its n-step samples (NStepReplayBuffer._get_samples): ``discounts`` multiplies the target Q.
+NStepReplaySamples = collections.namedtuple("NStepReplaySamples", ReplaySamples._fields + ("discounts",))
+
+MAX_N_STEPS = 32
+
+
+def discount_table(gamma, n_steps):
+    """``g[j] = float32(float(gamma) ** j)`` for ``j = 0 .. n_steps``: the power in double, rounded once."""
+    return [ctypes.c_float(float(gamma) ** j).value for j in range(int(n_steps) + 1)]
 
 
 class DeviceReplay:
@@ -61,7 +75,7 @@ class DeviceReplay:
     unstacked obs.  ``reward_dtype`` is the dtype ``put_step`` will be given.  There is no CPU fallback."""
 
     def __init__(self, num_envs, buffer_size, obs_width, act_dim, device, reward_dtype=torch.float32, n_stack=1,
-                 clear_keeps_sign=False, lib_path=None):
+                 clear_keeps_sign=False, lib_path=None, n_steps=1, gamma=0.99):
         n, size, W, A, k = int(num_envs), int(buffer_size), int(obs_width), int(act_dim), int(n_stack)
         if n <= 0 or size <= 0 or W <= 0 or A <= 0:
             raise ValueError("num_envs, buffer_size, obs_width and act_dim must be > 0")
@@ -69,6 +83,7 @@ class DeviceReplay:
             raise ValueError("n_stack must be in [1, 32] and divide obs_width")
         if reward_dtype not in (torch.float32, torch.float64):
             raise ValueError("reward_dtype must be torch.float32 or torch.float64")
+        self.set_n_steps(n_steps, gamma)
         device = _lib.cuda_device(device, "DeviceReplay")
         self.lib = _lib.load(lib_path)
         R = max(size // n, 1)
@@ -85,6 +100,16 @@ class DeviceReplay:
         self._bad = torch.zeros(1, dtype=torch.int32, device=device)
         self._puts = self._count = 0                    # put_obs calls; completed transitions
         self._bind()
+
+    def set_n_steps(self, n_steps, gamma):
+        """The constructor's ``n_steps`` and ``gamma`` (what ``gather_nstep`` uses), checked, and the
+        discount table built from them; nothing stored depends on either."""
+        if int(n_steps) != n_steps or not 1 <= n_steps <= MAX_N_STEPS:
+            raise ValueError(f"n_steps must be an integer in [1, {MAX_N_STEPS}]")
+        if not 0.0 <= float(gamma) <= 1.0:              # (refuses NaN as well)
+            raise ValueError("gamma must be in [0, 1]")
+        self.n_steps, self.gamma = int(n_steps), float(gamma)
+        self._table = (ctypes.c_float * (self.n_steps + 1))(*discount_table(self.gamma, self.n_steps))
 
     def _bind(self):
         """The C struct over the current buffers (again after a buffer was replaced)."""
@@ -188,6 +213,49 @@ class DeviceReplay:
             raise RuntimeError("sample from an empty buffer")
         idx = torch.randint(0, self.size * self.n, (batch_size,), device=self.device, generator=generator)
         return self.gather(idx)
+
+    def gather_nstep(self, idx, out=None):
+        """SB3's ``NStepReplayBuffer._get_samples`` (2.7: ``n_steps`` of SAC / TD3 / DQN) in one launch, with
+        the constructor's ``n_steps`` and ``gamma``: an ``NStepReplaySamples`` whose ``observations`` and
+        ``actions`` are those of ``gather(idx)``.  The run of a sample walks up to ``n_steps`` transitions
+        of its env and ends at the first that is done or timed out, or at the newest one stored (it crosses
+        neither the write position nor unwritten rows).  ``rewards`` [B, 1] is the discounted sum of the
+        run's rewards, ``next_observations`` and ``dones`` are those of its last transition (the window
+        rebuilt from the frame ring under that transition's own liveness), and ``discounts`` [B, 1] is
+        ``gamma ** (transitions in the run)``: the target is ``rewards + (1 - dones) * discounts * q_next``.
+        tests/replay_nstep_ref.py is the definition, met bit for bit: the table ``float32(gamma ** j)`` is
+        built once on the host with the power taken in double, and the sum is float32 in the order of the
+        steps, each product and each sum rounded on its own; a run of one transition returns the stored
+        reward's bits.  Two differences from SB3: it takes ``gamma ** float32`` in float32 (within 1 ulp of
+        the table: about 6e-8 on ``discounts``, at most 4.8e-7 observed on returns of unit-normal rewards),
+        and it adds the terms behind the run's end as ``+0.0``, which shows only for a return of ``-0.0``
+        (NumPy's own order of summation also differs from ``n_steps = 8`` on).  ``out``, bad indices, the
+        stream and the call order are as in ``gather``; there is no host sync."""
+        if self._puts != self._count:
+            raise RuntimeError("gather_nstep between put_obs and put_step: finish the step first")
+        B = int(idx.shape[0]) if idx.dim() == 1 else 0
+        if idx.dtype != torch.int64 or not 0 < B < 2 ** 31 or idx.device != self.device:
+            raise ValueError(f"idx must be a non-empty 1-D int64 tensor (below 2^31 indices) on {self.device}")
+        idx = idx.contiguous()
+        shapes = ((B, self.w), (B, self.a), (B, self.w), (B, 1), (B, 1), (B, 1))
+        if out is None:
+            out = NStepReplaySamples(*(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes))
+        else:
+            for name, t, s in zip(NStepReplaySamples._fields, out, shapes):
+                _lib.check_tensor(f"out.{name}", t, torch.float32, s, self.device)
+        _lib.check(self.lib.usv_replay_gather_nstep(self._rp, self._count, _ptr(idx), B, self.n_steps, self._table,
+                                                    *(_ptr(t) for t in out), self._stream()), self.lib)
+        return out if isinstance(out, NStepReplaySamples) else NStepReplaySamples(*out)
+
+    def sample_nstep(self, batch_size, generator=None):
+        """``sample`` for n-step returns: the same one device ``randint``, then ``gather_nstep``."""
+        batch_size = int(batch_size)
+        if batch_size <= 0:
+            raise ValueError("batch_size must be > 0")
+        if self.size == 0:
+            raise RuntimeError("sample from an empty buffer")
+        idx = torch.randint(0, self.size * self.n, (batch_size,), device=self.device, generator=generator)
+        return self.gather_nstep(idx)
 
     def clear(self):
         """Start over: the next ``put_obs`` is step 0 and stores its whole window.  ``bad_indices`` keeps

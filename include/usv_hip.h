@@ -707,6 +707,28 @@ int usv_replay_put_step(const usv_replay* rp, int64_t c, const void* rew_dev, in
 int usv_replay_gather(const usv_replay* rp, int64_t count, const int64_t* idx_dev, int32_t B, float* obs_out,
                       float* act_out, float* next_obs_out, float* done_out, float* rew_out, void* stream);
 
+/* N-step sampling: SB3 2.7's NStepReplayBuffer._get_samples on the same ring, one launch (ABI v5 addition;
+ * usv_replay and what is stored do not change).  tests/replay_nstep_ref.py restates it.  For i = idx[b] =
+ * slot * n + e and last = (count - 1) % R, the run walks s_j = (slot + j) % R, j = 0 .. n_steps - 1, and ends
+ * at m: the first j with done[s_j], timeout[s_j] or s_j == last (a run crosses neither the write position
+ * nor unwritten rows), else n_steps - 1.
+ *   obs_out[b], act_out[b]: those of (slot, e), as usv_replay_gather writes them;
+ *   next_obs_out[b]: the next_obs of transition (s_m, e), rebuilt from the frame ring under that
+ *   transition's own liveness; done_out[b] = float32(done) * (1 - float32(timeout)) of (s_m, e);
+ *   rew_out[b] = rew[s_0] if m == 0 (the stored bits), else the float32 sum in the order j = 0 .. m of
+ *   fl(rew[s_j] * g[j]), each product and each sum rounded to nearest on its own (no fused multiply-add);
+ *   discount_out[b] = g[m + 1], the factor of the target Q.
+ * discount_table_host is g[0 .. n_steps] in host memory, read during the call and passed to the kernel by
+ * value: the caller's float32(gamma ** j), the power taken in double (g[0] = 1).
+ * Two documented differences from SB3: it computes gamma ** float32 in float32 (within 1 ulp of such a
+ * table), and it adds the terms behind m as +0.0 (visible only for a return of -0.0).
+ * A bad idx gives NaN in all six outputs and counts in *bad_count.  The preconditions are those of
+ * usv_replay_gather.  USV_ERR_ARG, before any HIP call, for everything usv_replay_gather refuses, n_steps
+ * outside [1, 32], a NULL table or a table entry that is not finite. */
+int usv_replay_gather_nstep(const usv_replay* rp, int64_t count, const int64_t* idx_dev, int32_t B, int32_t n_steps,
+                            const float* discount_table_host /* [n_steps + 1] */, float* obs_out, float* act_out,
+                            float* next_obs_out, float* done_out, float* rew_out, float* discount_out, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
