@@ -30,6 +30,14 @@ is a compact SAC with config_sac's hyper-parameters where they carry over:
   fourth step and its ``env_actions`` feed ``env.step``, and a second head of ``batch_size`` rows with another
   seed serves both actor calls of a gradient step under one epoch, as ``SAC.train``'s ``reset_noise`` does.
   Without it the actor's noise is torch's (a state-independent tanh-Gaussian) and nothing here changes.
+* ``loss_kernel=True`` (``--loss-kernel``): the TD target with the twin-critic loss, the actor loss with the
+  entropy-coefficient loss, and ``polyak_update`` through ``gym_usv_amd.DeviceSACLoss`` / ``DevicePolyak``: one HIP
+  launch each forward, one each backward, in place of torch's op-by-op graphs and the 24 launches of the two-op
+  Polyak loop.  The entropy optimizer then steps after the actor loss's backward (one backward serves both
+  losses); ``ent`` is read before it either way, so the algorithm is SB3's.
+* ``check_loss=True`` (``--check-loss``, with ``loss_kernel``) also evaluates the torch lines on every gradient step
+  and records the largest differences of the three losses, each over the sum of the magnitudes of its terms, and
+  of Polyak against the torch two-op update of a cloned target (read back once per round: a test mode).
 
 ``learning_starts`` counts vector steps here (SB3 counts transitions: 50 000 of them are 12 steps of 4096 envs).  The loop
 collects ``train_freq`` steps, then takes ``gradient_steps`` gradient steps, as SB3's ``learn`` does.
@@ -38,6 +46,7 @@ bitwise reproducible.
 
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel
+    python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel --loss-kernel
 """
 from __future__ import annotations
 
@@ -172,8 +181,9 @@ class TorchReplay:
 
 
 class SAC:
-    def __init__(self, env, seed=0, device_replay=True, check_replay=False, sde_kernel=False, **cfg):
-        from gym_usv_amd import DeviceReplay, DeviceSDE
+    def __init__(self, env, seed=0, device_replay=True, check_replay=False, sde_kernel=False, loss_kernel=False,
+                 check_loss=False, **cfg):
+        from gym_usv_amd import DevicePolyak, DeviceReplay, DeviceSACLoss, DeviceSDE
         from gym_usv_amd.replay import discount_table
         from gym_usv_amd.wrappers import DeviceWrappers
         self.cfg = c = dict(CONFIG_SAC, **cfg)
@@ -198,6 +208,14 @@ class SAC:
             self.head_env = DeviceSDE(self.N, c["net_arch"][-1], A, d, seed + 1, lo, hi)
             self.head_mb = DeviceSDE(c["batch_size"], c["net_arch"][-1], A, d, seed + 2, lo, hi)
         self.sde_steps = 0
+        if check_loss and not loss_kernel:
+            raise ValueError("check_loss compares the loss kernels with torch: it needs loss_kernel=True")
+        self.loss = self.polyak = None
+        if loss_kernel:
+            self.loss = DeviceSACLoss(d)
+            self.polyak = DevicePolyak(list(self.critic.parameters()), list(self.target.parameters()))
+        self.check_loss, self.losses_checked = check_loss, 0
+        self.loss_diff = torch.zeros(5, device=d)           # critic, actor, ent_coef, Polyak |diff|, Polyak ratio
         self.wr = DeviceWrappers(self.N, D, k, d, env.reward.dtype)
         self.rb = self.shadow = None
         if device_replay or check_replay:
@@ -260,6 +278,70 @@ class SAC:
         s = self.actor.sde(obs, self.head_mb)
         return s.actions, s.log_prob
 
+    def kernel_step(self, mb, a_pi, logp, ent):
+        """The rest of a gradient step through the loss kernels: (actor_loss, critic_loss, ent_coef_loss)."""
+        c = self.cfg
+        with torch.no_grad():
+            a2, logp2 = self.policy(mb.next_observations)
+            q1n, q2n = self.target(mb.next_observations, a2)
+        q1, q2 = self.critic(mb.observations, mb.actions)
+        cl = self.loss.critic(q1, q2, q1n, q2n, mb.rewards, mb.dones, ent_coef=ent, logp_next=logp2,
+                              discounts=mb.discounts)
+        if self.check_loss:
+            self.compare_critic(cl, q1, q2, q1n, q2n, logp2, mb, ent)
+        self.opt_c.zero_grad(set_to_none=True)
+        cl.loss.backward()
+        self.opt_c.step()
+        q1p, q2p = self.critic(mb.observations, a_pi)
+        pl = self.loss.policy(logp, q1p, q2p, ent, log_ent_coef=self.log_ent, target_entropy=self.target_entropy)
+        if self.check_loss:
+            self.compare_policy(pl, logp, q1p, q2p, ent)
+        self.opt_a.zero_grad(set_to_none=True)
+        self.opt_e.zero_grad(set_to_none=True)
+        (pl.actor_loss + pl.ent_coef_loss).backward()       # one backward launch for logp, both q's and log_ent
+        self.opt_a.step()
+        self.opt_e.step()
+        ref = None
+        if self.check_loss:                                 # the torch two-op update of a cloned target
+            with torch.no_grad():
+                ref = [(t.clone(), t * (1 - c["tau"]), c["tau"] * p) for p, t in zip(self.critic.parameters(),
+                                                                                     self.target.parameters())]
+                for (t, _, _), p in zip(ref, self.critic.parameters()):
+                    t.mul_(1 - c["tau"]).add_(p, alpha=c["tau"])
+        self.polyak.step(c["tau"])
+        if ref is not None:
+            with torch.no_grad():
+                diff = torch.cat([(t - r).abs().flatten() for t, (r, _, _) in zip(self.target.parameters(), ref)])
+                size = torch.cat([(a.abs() + b.abs()).flatten() for _, a, b in ref])
+                self._worst(3, diff.max(), 1.0)
+                self._worst(4, torch.where(size > 0, diff / size, diff * float("inf")).nan_to_num(nan=0.0).max(), 1.0)
+            self.losses_checked += 1
+        return pl.actor_loss.detach(), cl.loss.detach(), pl.ent_coef_loss.detach()
+
+    def _worst(self, at, diff, scale):
+        scale = torch.as_tensor(scale, device=diff.device, dtype=diff.dtype)
+        r = torch.where(scale > 0, diff / scale, diff * float("inf")).nan_to_num(nan=0.0)   # a zero scale wants a zero diff
+        self.loss_diff[at] = torch.maximum(self.loss_diff[at], r.detach())
+
+    @torch.no_grad()
+    def compare_critic(self, cl, q1, q2, q1n, q2n, logp2, mb, ent):
+        """The torch lines of the critic loss on the same tensors; the difference over the sum of magnitudes."""
+        q_next = torch.min(q1n, q2n) - ent * logp2[:, None]
+        target = mb.rewards + (1 - mb.dones) * mb.discounts * q_next
+        loss = 0.5 * (F.mse_loss(q1, target) + F.mse_loss(q2, target))
+        n = mb.rewards.abs() + ((1 - mb.dones) * mb.discounts).abs() * (torch.min(q1n, q2n).abs() + (ent * logp2[:, None]).abs())
+        scale = 0.5 * (((q1.abs() + n) ** 2).mean() + ((q2.abs() + n) ** 2).mean())
+        self._worst(0, (cl.loss - loss).abs(), scale)
+
+    @torch.no_grad()
+    def compare_policy(self, pl, logp, q1p, q2p, ent):
+        q_pi = torch.min(q1p, q2p)
+        actor = (ent * logp[:, None] - q_pi).mean()
+        ent_loss = -(self.log_ent * (logp + self.target_entropy)).mean()
+        self._worst(1, (pl.actor_loss - actor).abs(), ((ent * logp[:, None]).abs() + q_pi.abs()).mean())
+        self._worst(2, (pl.ent_coef_loss - ent_loss).abs(),
+                    self.log_ent.abs().squeeze() * (logp.abs() + abs(self.target_entropy)).mean())
+
     def train(self, gradient_steps):
         c, stats = self.cfg, []
         for _ in range(gradient_steps):
@@ -268,6 +350,10 @@ class SAC:
                 self.head_mb.reset_noise()                  # SAC.train: one matrix per gradient step
             a_pi, logp = self.policy(mb.observations)
             ent = self.log_ent.detach().exp()
+            if self.loss is not None:
+                actor_loss, critic_loss, ent_loss = self.kernel_step(mb, a_pi, logp, ent)
+                stats.append(torch.stack((actor_loss, critic_loss, ent.squeeze(), ent_loss)))
+                continue
             ent_loss = -(self.log_ent * (logp.detach() + self.target_entropy)).mean()
             self.opt_e.zero_grad(set_to_none=True)
             ent_loss.backward()
@@ -292,6 +378,9 @@ class SAC:
             stats.append(torch.stack((actor_loss.detach(), critic_loss.detach(), ent.squeeze(), ent_loss.detach())))
         s = torch.stack(stats).mean(0).tolist()
         out = {"actor_loss": s[0], "critic_loss": s[1], "ent_coef": s[2], "ent_coef_loss": s[3]}
+        if self.check_loss:                                 # the largest so far, one read per round
+            out["loss_diff"] = dict(zip(("critic", "actor", "ent_coef", "polyak_abs", "polyak_ratio"), self.loss_diff.tolist()))
+            out["losses_checked"] = self.losses_checked
         if self.head_mb is not None:                        # of the round's last gradient step
             ls = self.actor.log_std
             out["log_std_mean"], out["log_std_move_abs_max"], out["log_std_grad_abs_max"] = torch.stack(
@@ -308,13 +397,16 @@ class SAC:
 
 
 def train(env_id="usv-simple", envs=4096, steps=400, seed=0, log=print, device_replay=True, check_replay=False,
-          max_episode_steps=None, sde_kernel=False, **cfg):
+          max_episode_steps=None, sde_kernel=False, loss_kernel=False, check_loss=False, **cfg):
     """``steps`` vector steps of ``envs`` envs.  Returns one record per training round (``train_freq``
     steps, then ``gradient_steps`` gradient steps once ``learning_starts`` steps are in the buffer)."""
     import gym_usv_amd
+    if check_loss and not loss_kernel:
+        raise ValueError("check_loss compares the loss kernels with torch: it needs loss_kernel=True")
     kw = {} if max_episode_steps is None else {"max_episode_steps": max_episode_steps}
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False, **kw)
-    sac = SAC(env, seed=seed, device_replay=device_replay, check_replay=check_replay, sde_kernel=sde_kernel, **cfg)
+    sac = SAC(env, seed=seed, device_replay=device_replay, check_replay=check_replay, sde_kernel=sde_kernel,
+              loss_kernel=loss_kernel, check_loss=check_loss, **cfg)
     c, hist, done_steps = sac.cfg, [], 0
     t0 = time.perf_counter()
     while done_steps < steps:
@@ -346,9 +438,12 @@ def main():
     ap.add_argument("--sde-kernel", action="store_true", help="gSDE (config_sac's use_sde) through DeviceSDE.squashed")
     ap.add_argument("--n-steps", type=int, default=CONFIG_SAC["n_steps"],
                     help="n-step returns (SB3 2.7's n_steps) through sample_nstep; 1: the one-step target")
+    ap.add_argument("--loss-kernel", action="store_true",
+                    help="critic, actor and entropy-coefficient losses and Polyak through DeviceSACLoss / DevicePolyak")
+    ap.add_argument("--check-loss", action="store_true", help="with --loss-kernel: also run the torch lines and compare")
     a = ap.parse_args()
     train(a.env_id, a.envs, a.steps, a.seed, device_replay=a.device_replay, check_replay=a.check_replay,
-          sde_kernel=a.sde_kernel, buffer_size=a.buffer_size, batch_size=a.batch_size, n_steps=a.n_steps)
+          sde_kernel=a.sde_kernel, loss_kernel=a.loss_kernel, check_loss=a.check_loss, buffer_size=a.buffer_size, batch_size=a.batch_size, n_steps=a.n_steps)
 
 
 if __name__ == "__main__":

@@ -30,6 +30,9 @@
 //   usv_replay_math.hpp   replay buffer: slots, frame rows, age and live masks, n-step runs (host C++, no HIP)
 //   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather /
 //                         _gather_nstep)
+//   usv_sac_math.hpp      SAC update: TD target, losses, unit gradients, the sums' order, Polyak (host C++, no HIP)
+//   usv_sac.hpp           SAC update: fused critic and policy losses, their backward, Polyak over a tensor list
+//                         (usv_sac_critic_loss / _policy_loss / _loss_backward / usv_polyak_update)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -58,7 +61,8 @@
 #include "usv_rollout.hpp"
 #include "usv_rollout_frames.hpp"
 #include "usv_sde.hpp"
-#include "usv_replay.hpp"        // (last: every kernel before it keeps its place in the code object)
+#include "usv_replay.hpp"
+#include "usv_sac.hpp"           // (last: every kernel before it keeps its place in the code object)
 
 // ============================================================================= host side
 using namespace usv;
@@ -1540,6 +1544,150 @@ int usv_replay_gather_nstep(const usv_replay* rp, int64_t count, const int64_t* 
   hipLaunchKernelGGL(replay_gather_nstep_kernel, grid, block, 0, (hipStream_t)stream, a, rp_laps(count, a.R, a.k),
                      (long long)rp_size(count, a.R), idx, (int)B, (int)n_steps, tab, obs_out, act_out, next_obs_out,
                      done_out, rew_out, discount_out);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- fused SAC update (usv_sac.hpp)
+static int sac_bufs(const Buf* b, size_t nb, int& dev) {
+  switch (check_bufs(b, nb)) {
+    case kBufNull: return fail(USV_ERR_ARG, "usv_sac: null buffer");
+    case kBufAlign: return fail(USV_ERR_ARG, "usv_sac: scratch is not 16-B aligned or a buffer is not 4-B aligned");
+    default: break;
+  }
+  if (check_bufs(b, nb, &dev) == kBufDevice)
+    return fail(USV_ERR_ARG, dev < 0 ? "usv_sac: the first buffer is not a device pointer"
+                                     : "usv_sac: a buffer is not a device pointer on the device that holds the first");
+  return USV_OK;
+}
+
+size_t usv_sac_scratch_floats(int32_t rows) { return rows >= 1 ? sac_scratch_floats(rows) : 0; }
+
+int usv_sac_critic_loss(int32_t rows, const float* q1, const float* q2, const float* q1_next, const float* q2_next,
+                        const float* rewards, const float* dones, const float* ent, const float* logp_next,
+                        const float* discounts, float gamma, float* target, float* loss, float* g_q1, float* g_q2,
+                        float* scratch, void* stream) {
+  int dev;
+  if (rows < 1) return fail(USV_ERR_ARG, "usv_sac_critic_loss: rows must be >= 1");
+  if ((ent != nullptr) != (logp_next != nullptr))
+    return fail(USV_ERR_ARG, "usv_sac_critic_loss: ent and logp_next must be both NULL or both set");
+  const Buf all[] = {{scratch, 16},    {q1, 4},       {q2, 4},           {q1_next, 4},        {q2_next, 4},
+                     {rewards, 4},     {dones, 4},    {target, 4},       {loss, 4},           {ent, 4, true},
+                     {logp_next, 4, true}, {discounts, 4, true}, {g_q1, 4, true}, {g_q2, 4, true}};
+  if (int rc = sac_bufs(all, 14, dev)) return rc;
+  DeviceGuard g(dev);
+  const SacCriticArgs a{rows, q1, q2, q1_next, q2_next, rewards, dones, ent, logp_next, discounts, gamma,
+                        target, loss, g_q1, g_q2, scratch};
+  hipLaunchKernelGGL(sac_critic_kernel, dim3((unsigned)sac_partials(rows)), dim3(kBlock), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_sac_policy_loss(int32_t rows, const float* logp, const float* q1_pi, const float* q2_pi, const float* ent,
+                        const float* log_ent, float target_entropy, float* actor_loss, float* ent_loss, float* g_logp,
+                        float* g_q1, float* g_q2, float* g_log_ent, float* scratch, void* stream) {
+  int dev;
+  if (rows < 1) return fail(USV_ERR_ARG, "usv_sac_policy_loss: rows must be >= 1");
+  if (log_ent && !ent_loss) return fail(USV_ERR_ARG, "usv_sac_policy_loss: log_ent needs ent_loss");
+  const Buf all[] = {{scratch, 16},      {logp, 4},          {q1_pi, 4},        {q2_pi, 4},       {ent, 4},
+                     {actor_loss, 4},    {log_ent, 4, true}, {ent_loss, 4, true}, {g_logp, 4, true}, {g_q1, 4, true},
+                     {g_q2, 4, true},    {g_log_ent, 4, true}};
+  if (int rc = sac_bufs(all, 12, dev)) return rc;
+  DeviceGuard g(dev);
+  const SacPolicyArgs a{rows, logp, q1_pi, q2_pi, ent, log_ent, target_entropy, actor_loss, ent_loss, g_logp,
+                        g_q1, g_q2, g_log_ent, scratch};
+  hipLaunchKernelGGL(sac_policy_kernel, dim3((unsigned)sac_partials(rows)), dim3(kBlock), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_sac_loss_backward(int32_t rows, const float* up, const float* g1, const float* g2, const float* g3, float* o1,
+                          float* o2, float* o3, const float* up_s, const float* gs, float* os, void* stream) {
+  int dev;
+  if (rows < 1) return fail(USV_ERR_ARG, "usv_sac_loss_backward: rows must be >= 1");
+  if ((o2 && !g2) || (o3 && !g3) || (os && !gs))
+    return fail(USV_ERR_ARG, "usv_sac_loss_backward: an output is given without its unit gradient");
+  const Buf all[] = {{o1, 4},       {g1, 4},       {up, 4, true},   {g2, 4, true}, {g3, 4, true}, {o2, 4, true},
+                     {o3, 4, true}, {up_s, 4, true}, {gs, 4, true}, {os, 4, true}};
+  if (int rc = sac_bufs(all, 10, dev)) return rc;
+  DeviceGuard g(dev);
+  const SacScaleArgs a{rows, up, {g1, g2, g3}, {o1, o2, o3}, up_s, gs, os};
+  hipLaunchKernelGGL(sac_scale_kernel, dim3((unsigned)(((int64_t)rows + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// The pairs that hold elements and their chunks; a refusal's message, or null.
+static const char* polyak_count(const usv_polyak_pair* pairs, int32_t n, int64_t& live, int64_t& chunks) {
+  live = chunks = 0;
+  if (!pairs) return "usv_polyak_update: null pairs";
+  if (n < 1) return "usv_polyak_update: n_pairs must be >= 1";
+  for (int32_t i = 0; i < n; ++i) {
+    const usv_polyak_pair& p = pairs[i];
+    if (p.numel < 0) return "usv_polyak_update: numel must be >= 0";
+    if (p.numel == 0) continue;
+    if (!p.src || !p.dst) return "usv_polyak_update: null src or dst";
+    if (((reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.dst)) & 3) != 0)
+      return "usv_polyak_update: src or dst is not 4-B aligned";
+    if (p.src == p.dst) return "usv_polyak_update: src and dst are the same address";
+    ++live;
+    chunks += polyak_chunks(p.numel);
+  }
+  if (chunks > 2147483647) return "usv_polyak_update: above 2^31 - 1 chunks of 4096 elements";
+  return nullptr;
+}
+static size_t polyak_bytes(int64_t live, int64_t chunks) {
+  return (size_t)live * sizeof(PolyakPair) + (size_t)chunks * sizeof(PolyakChunk);
+}
+
+size_t usv_polyak_table_bytes(const usv_polyak_pair* pairs, int32_t n_pairs) {
+  int64_t live, chunks;
+  return polyak_count(pairs, n_pairs, live, chunks) ? 0 : polyak_bytes(live, chunks);
+}
+
+int usv_polyak_update(const usv_polyak_pair* pairs, int32_t n_pairs, void* table, size_t table_bytes, int32_t upload,
+                      double tau, void* stream) {
+  int64_t live, chunks;
+  int dev;
+  if (const char* why = polyak_count(pairs, n_pairs, live, chunks)) return fail(USV_ERR_ARG, why);
+  if (!polyak_tau_ok(tau)) return fail(USV_ERR_ARG, "usv_polyak_update: tau must be in [0, 1]");
+  if (live == 0) return USV_OK;
+  if (!table) return fail(USV_ERR_ARG, "usv_polyak_update: null table");
+  if ((reinterpret_cast<uintptr_t>(table) & 7) != 0) return fail(USV_ERR_ARG, "usv_polyak_update: the table is not 8-B aligned");
+  if (table_bytes < polyak_bytes(live, chunks)) return fail(USV_ERR_ARG, "usv_polyak_update: the table is too small");
+  std::vector<Buf> bufs = {{table, 8}};
+  if (upload)
+    for (int32_t i = 0; i < n_pairs; ++i)
+      if (pairs[i].numel > 0) {
+        bufs.push_back(Buf{pairs[i].src, 4});
+        bufs.push_back(Buf{pairs[i].dst, 4});
+      }
+  if (check_bufs(bufs.data(), bufs.size(), &dev) == kBufDevice)
+    return fail(USV_ERR_ARG, dev < 0 ? "usv_polyak_update: the table is not a device pointer"
+                                     : "usv_polyak_update: a tensor is not a device pointer on the table's device");
+  DeviceGuard g(dev);
+  static_assert(sizeof(PolyakPair) == 24 && sizeof(PolyakChunk) == 8, "the table's layout");
+  if (upload) {
+    std::vector<unsigned char> host(polyak_bytes(live, chunks));
+    PolyakPair* const hp = reinterpret_cast<PolyakPair*>(host.data());
+    PolyakChunk* const hc = reinterpret_cast<PolyakChunk*>(host.data() + (size_t)live * sizeof(PolyakPair));
+    int64_t at = 0, c = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+      if (pairs[i].numel == 0) continue;
+      hp[at] = PolyakPair{pairs[i].src, pairs[i].dst, (long long)pairs[i].numel};
+      for (int64_t k = 0; k < polyak_chunks(pairs[i].numel); ++k) hc[c++] = PolyakChunk{(int)at, (int)k};
+      ++at;
+    }
+    HIP_TRY(hipDeviceSynchronize());                 // launches in flight may read the old table
+    HIP_TRY(hipMemcpy(table, host.data(), host.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  float tau_f, om;
+  polyak_coeffs(tau, tau_f, om);
+  const PolyakPair* const dp = (const PolyakPair*)table;
+  const PolyakChunk* const dc = (const PolyakChunk*)((const char*)table + (size_t)live * sizeof(PolyakPair));
+  hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)chunks), dim3(kBlock), 0, (hipStream_t)stream, dp, dc, tau_f, om);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

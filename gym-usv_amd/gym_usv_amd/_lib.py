@@ -123,6 +123,11 @@ class UsvReplay(ctypes.Structure):
                 ("bad_count", ctypes.c_void_p)]
 
 
+class UsvPolyakPair(ctypes.Structure):
+    """usv_polyak_pair: one (parameters, target parameters) tensor pair of usv_polyak_update."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("numel", ctypes.c_int64)]
+
+
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
 _i64, _u32, _f32 = ctypes.c_int64, ctypes.c_uint32, ctypes.c_float
@@ -188,6 +193,13 @@ SIGNATURES = [
     ("usv_replay_gather", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("usv_replay_gather_nstep", ctypes.c_int, [ctypes.POINTER(UsvReplay), _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                                _vp, _vp, _vp]),
+    ("usv_sac_scratch_floats", _sz, [_i32]),
+    ("usv_sac_critic_loss", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp,
+                                           _vp, _vp]),
+    ("usv_sac_policy_loss", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_sac_loss_backward", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_polyak_table_bytes", _sz, [ctypes.POINTER(UsvPolyakPair), _i32]),
+    ("usv_polyak_update", ctypes.c_int, [ctypes.POINTER(UsvPolyakPair), _i32, _vp, _sz, _i32, ctypes.c_double, _vp]),
 ]
 
 _LIBS = {}

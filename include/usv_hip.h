@@ -729,6 +729,61 @@ int usv_replay_gather_nstep(const usv_replay* rp, int64_t count, const int64_t* 
                             const float* discount_table_host /* [n_steps + 1] */, float* obs_out, float* act_out,
                             float* next_obs_out, float* done_out, float* rew_out, float* discount_out, void* stream);
 
+/* ---- Fused SAC update: SB3's SAC.train lines for the TD target, the twin-critic loss, the actor and
+ * entropy-coefficient losses (sac/sac.py; TD3's target without the entropy term) and common/utils.py's
+ * polyak_update (ABI v5 additions).  Handle-free and stream-ordered like the usv_sde_* entries: the caller supplies
+ * every buffer, f32 on one device and 4-B aligned; USV_ERR_ARG with a usv_last_error message, before any launch, for
+ * what is refused.  The arithmetic and the fixed summation order are gym-usv_amd/csrc/usv_sac_math.hpp's;
+ * tests/sac_loss_ref.py restates them.  All scalars that training changes (ent, log_ent, the upstream gradients) are
+ * device scalars: no entry reads the device.
+ *
+ * scratch: usv_sac_scratch_floats(rows) floats (0 for rows < 1), 16-B aligned, zeroed once when it is allocated;
+ * a call leaves its first word zero again.  Calls that share a scratch must be stream-ordered.  The losses do not
+ * depend on the grid, the stream or the order in which blocks end: they are bitwise reproducible.
+ *
+ * usv_sac_critic_loss, rows [rows] each:
+ *   qn = min(q1_next, q2_next) (a NaN stays);  with ent and logp_next  qn -= ent[0] * logp_next
+ *   target = rewards + ((1 - dones) * disc) * qn      disc = discounts[i], or gamma where discounts is NULL
+ *   loss[0] = 0.5 * (mean((q1 - target)^2) + mean((q2 - target)^2))
+ *   g_q1 = (q1 - target) / rows, g_q2 likewise: the gradients at unit upstream (both optional: NULL under no_grad)
+ * ent and logp_next come together (both NULL: TD3's target).
+ *
+ * usv_sac_policy_loss:
+ *   actor_loss[0] = mean(ent[0] * logp - min(q1_pi, q2_pi))
+ *   ent_loss[0]   = -mean(log_ent[0] * (logp + target_entropy))       only with log_ent (then ent_loss is required)
+ *   g_logp = ent / rows;  g_q1 = -w / rows, g_q2 = -(1 - w) / rows, w = 1, 0.5, 0 for q1_pi <, ==, > q2_pi
+ *   g_log_ent[0] = -mean(logp + target_entropy)
+ * ent is data; every g_* is optional.
+ *
+ * usv_sac_loss_backward: o_k[i] = g_k[i] * up[0] for the up-to-three row gradients whose o_k is given (o1 is
+ * required), and os[0] = gs[0] * up_s[0] where os is given.  A NULL up (up_s) writes zeros: the loss took no part
+ * in what was differentiated.
+ *
+ * usv_polyak_update: dst = (dst * float(1 - tau)) + (float(tau) * src) over n_pairs tensor pairs in one launch, 1 - tau
+ * taken in double.  pairs_host is read during the call.  table_dev: usv_polyak_table_bytes' worth of device memory,
+ * 8-B aligned, that the call fills (after a device synchronise, and synchronising again) when upload != 0 and only
+ * reads otherwise: upload whenever pairs_host has changed.  Pairs with numel == 0 are skipped (their pointers are not
+ * looked at); a call with nothing left launches nothing.  Refused: n_pairs < 1, a NULL pointer, numel < 0, a pointer
+ * that is not 4-B aligned, src == dst, tau outside [0, 1], a table that is too small. */
+typedef struct usv_polyak_pair {
+  const float* src;            /* the parameters */
+  float* dst;                  /* the target's, updated in place */
+  int64_t numel;
+} usv_polyak_pair;
+size_t usv_sac_scratch_floats(int32_t rows);
+int usv_sac_critic_loss(int32_t rows, const float* q1, const float* q2, const float* q1_next, const float* q2_next,
+                        const float* rewards, const float* dones, const float* ent, const float* logp_next,
+                        const float* discounts, float gamma, float* target, float* loss, float* g_q1, float* g_q2,
+                        float* scratch, void* stream);
+int usv_sac_policy_loss(int32_t rows, const float* logp, const float* q1_pi, const float* q2_pi, const float* ent,
+                        const float* log_ent, float target_entropy, float* actor_loss, float* ent_loss, float* g_logp,
+                        float* g_q1, float* g_q2, float* g_log_ent, float* scratch, void* stream);
+int usv_sac_loss_backward(int32_t rows, const float* up, const float* g1, const float* g2, const float* g3, float* o1,
+                          float* o2, float* o3, const float* up_s, const float* gs, float* os, void* stream);
+size_t usv_polyak_table_bytes(const usv_polyak_pair* pairs_host, int32_t n_pairs);
+int usv_polyak_update(const usv_polyak_pair* pairs_host, int32_t n_pairs, void* table_dev, size_t table_bytes,
+                      int32_t upload, double tau, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
