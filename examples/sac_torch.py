@@ -38,6 +38,18 @@ is a compact SAC with config_sac's hyper-parameters where they carry over:
 * ``check_loss=True`` (``--check-loss``, with ``loss_kernel``) also evaluates the torch lines on every gradient step
   and records the largest differences of the three losses, each over the sum of the magnitudes of its terms, and
   of Polyak against the torch two-op update of a cloned target (read back once per round: a test mode).
+* ``caps=True`` (``--caps``): config_sac's ``lambda_t=10``, ``lambda_s=5``, ``eps_s=0.1``, the CAPS regulariser of the
+  SB3 fork the reference trains with (Mysore et al., ICRA 2021): the actor loss gains ``lambda_t * L_T + lambda_s *
+  L_S`` with ``L_T = ||pi(s) - pi(s')||_2`` and ``L_S = ||pi(s) - pi(s + eps_s * z)||_2``, ``z ~ N(0, I)``, averaged over
+  the minibatch; pi is the deterministic action, ``tanh(hardtanh(mu))`` with ``sde_kernel`` and ``tanh(mu)`` without.
+  The mean at ``s`` is the one the actor forward behind ``a_pi`` computes; one more forward takes the ``2 B`` rows of
+  ``s'`` and the perturbed ``s``.  In torch lines (``randn_like``, ``linalg.vector_norm``) unless
+* ``caps_kernel=True`` (``--caps-kernel``, with ``caps``) routes it through ``gym_usv_amd.DeviceCAPS``: one launch for
+  the perturbed observations (counter-based noise, a new epoch every gradient step), one for both terms with their
+  gradients, one backward.  ``check_caps=True`` (``--check-caps``, with ``caps_kernel``) also evaluates the torch lines
+  on the kernel's own perturbed observations and records the largest difference of the loss over the loss (read back
+  once per round: a test mode).  The temporal term needs the one-step successor: ``caps`` with ``n_steps`` other than 1
+  is a ``ValueError``.
 
 ``learning_starts`` counts vector steps here (SB3 counts transitions: 50 000 of them are 12 steps of 4096 envs).  The loop
 collects ``train_freq`` steps, then takes ``gradient_steps`` gradient steps, as SB3's ``learn`` does.
@@ -47,6 +59,7 @@ bitwise reproducible.
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel --loss-kernel
+    python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel --loss-kernel --caps --caps-kernel
 """
 from __future__ import annotations
 
@@ -69,7 +82,8 @@ import torch.nn.functional as F  # noqa: E402
 CONFIG_SAC = {"n_stack": 5, "net_arch": (400, 300), "lr": 1e-4, "gamma": 0.99, "tau": 0.005, "buffer_size": 400000,
               "batch_size": 256, "train_freq": 8, "gradient_steps": 8, "learning_starts": 12,
               "n_steps": 1,                                         # SB3 2.7's n_steps (config_sac has none: 1)
-              "sde_sample_freq": 4, "log_std_init": -3.0}             # the last two: sde_kernel=True only
+              "sde_sample_freq": 4, "log_std_init": -3.0,             # these two: sde_kernel=True only
+              "lambda_t": 10.0, "lambda_s": 5.0, "eps_s": 0.1}        # CAPS (config.py:34-36): caps=True only
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0   # SB3 sac/policies.py
 CLIP_MEAN = 2.0                         # SB3 sac/policies.py, with use_sde
 
@@ -94,19 +108,26 @@ class Actor(nn.Module):
 
     def sde(self, obs, head):
         """gSDE through ``head.squashed``: its ``SquashedSample`` (actions in [-1, 1], Box actions,
-        log-probability, Gaussian actions).  StateDependentNoiseDistribution, squash_output, learn_features."""
+        log-probability, Gaussian actions) and the mean.  StateDependentNoiseDistribution, squash_output,
+        learn_features."""
         h = F.relu(self.body(obs))
-        return head.squashed(F.hardtanh(self.mu(h), -CLIP_MEAN, CLIP_MEAN), h, self.log_std.exp())
+        mean = F.hardtanh(self.mu(h), -CLIP_MEAN, CLIP_MEAN)
+        return head.squashed(mean, h, self.log_std.exp()), mean
 
     def forward(self, obs):
-        """(action in [-1, 1], its log-probability): SquashedDiagGaussianDistribution, epsilon 1e-6."""
+        """(action in [-1, 1], its log-probability, the mean): SquashedDiagGaussianDistribution, epsilon 1e-6."""
         h = F.relu(self.body(obs))
         mu, log_std = self.mu(h), self.log_std(h).clamp(LOG_STD_MIN, LOG_STD_MAX)
         std = log_std.exp()
         u = mu + std * torch.randn_like(mu)
         a = torch.tanh(u)
         logp = (-0.5 * ((u - mu) / std) ** 2 - log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
-        return a, logp - torch.log(1 - a * a + 1e-6).sum(-1)
+        return a, logp - torch.log(1 - a * a + 1e-6).sum(-1), mu
+
+    def mean(self, obs):
+        """The pre-squash mean of the deterministic action ``tanh(mean)``, as ``sde`` / ``forward`` compute it."""
+        mu = self.mu(F.relu(self.body(obs)))
+        return F.hardtanh(mu, -CLIP_MEAN, CLIP_MEAN) if isinstance(self.log_std, nn.Parameter) else mu
 
 
 class Critic(nn.Module):
@@ -182,8 +203,8 @@ class TorchReplay:
 
 class SAC:
     def __init__(self, env, seed=0, device_replay=True, check_replay=False, sde_kernel=False, loss_kernel=False,
-                 check_loss=False, **cfg):
-        from gym_usv_amd import DevicePolyak, DeviceReplay, DeviceSACLoss, DeviceSDE
+                 check_loss=False, caps=False, caps_kernel=False, check_caps=False, **cfg):
+        from gym_usv_amd import DeviceCAPS, DevicePolyak, DeviceReplay, DeviceSACLoss, DeviceSDE
         from gym_usv_amd.replay import discount_table
         from gym_usv_amd.wrappers import DeviceWrappers
         self.cfg = c = dict(CONFIG_SAC, **cfg)
@@ -216,6 +237,11 @@ class SAC:
             self.polyak = DevicePolyak(list(self.critic.parameters()), list(self.target.parameters()))
         self.check_loss, self.losses_checked = check_loss, 0
         self.loss_diff = torch.zeros(5, device=d)           # critic, actor, ent_coef, Polyak |diff|, Polyak ratio
+        check_caps_args(caps, caps_kernel, check_caps, c["n_steps"])
+        self.caps, self.caps_dev, self.check_caps, self.caps_checked = caps, None, check_caps, 0
+        if caps_kernel:                                     # rows = positions in the minibatch; its own seed
+            self.caps_dev = DeviceCAPS(d, seed + 3, c["lambda_t"], c["lambda_s"], c["eps_s"], squash=True)
+        self.caps_diff = torch.zeros((), device=d)
         self.wr = DeviceWrappers(self.N, D, k, d, env.reward.dtype)
         self.rb = self.shadow = None
         if device_replay or check_replay:
@@ -241,10 +267,10 @@ class SAC:
                 if self.sde_steps % self.cfg["sde_sample_freq"] == 0:
                     self.head_env.reset_noise()
                 self.sde_steps += 1
-                s = self.actor.sde(obs, self.head_env)      # the head's buffers: consumed before its next call
+                s, _ = self.actor.sde(obs, self.head_env)   # the head's buffers: consumed before its next call
                 a, a_env = s.actions, s.env_actions
             else:
-                a, _ = self.actor(obs)
+                a, _, _ = self.actor(obs)
             for buf in (self.rb, self.shadow):
                 if buf is not None:
                     buf.put_obs(obs, a)
@@ -272,17 +298,47 @@ class SAC:
         return mb
 
     def policy(self, obs):
-        """(action, log-probability) of the update's actor calls."""
+        """(action, log-probability, mean) of the update's actor calls."""
         if self.head_mb is None:
             return self.actor(obs)
-        s = self.actor.sde(obs, self.head_mb)
-        return s.actions, s.log_prob
+        s, mean = self.actor.sde(obs, self.head_mb)
+        return s.actions, s.log_prob, mean
 
-    def kernel_step(self, mb, a_pi, logp, ent):
+    @staticmethod
+    def smooth_lines(m, m2, m3, lambda_t, lambda_s):
+        """CAPS in torch lines from the three pre-squash means: (loss, temporal, spatial)."""
+        a = torch.tanh(m)
+        temporal = torch.linalg.vector_norm(a - torch.tanh(m2), dim=-1).mean()
+        spatial = torch.linalg.vector_norm(a - torch.tanh(m3), dim=-1).mean()
+        return lambda_t * temporal + lambda_s * spatial, temporal.detach(), spatial.detach()
+
+    def smooth(self, mb, m):
+        """The CAPS term of a gradient step, (loss, temporal, spatial), from the mean ``m`` at ``mb.observations``:
+        one actor forward over the 2 B rows of the next and the perturbed observations."""
+        c = self.cfg
+        if self.caps_dev is not None:
+            self.caps_dev.reset_noise()
+            near = self.caps_dev.near(mb.observations)
+        else:
+            near = mb.observations + c["eps_s"] * torch.randn_like(mb.observations)
+        m2, m3 = self.actor.mean(torch.cat((mb.next_observations, near))).chunk(2)
+        if self.caps_dev is None:
+            return self.smooth_lines(m, m2, m3, c["lambda_t"], c["lambda_s"])
+        s = self.caps_dev.loss(m, m2, m3)
+        if self.check_caps:
+            with torch.no_grad():
+                ref = self.smooth_lines(m, m2, m3, c["lambda_t"], c["lambda_s"])[0]
+                diff = (s.loss - ref).abs()
+                r = torch.where(ref > 0, diff / ref, diff * float("inf")).nan_to_num(nan=0.0)   # as _worst
+                self.caps_diff = torch.maximum(self.caps_diff, r)
+            self.caps_checked += 1
+        return s.loss, s.temporal, s.spatial
+
+    def kernel_step(self, mb, a_pi, logp, ent, smooth=None):
         """The rest of a gradient step through the loss kernels: (actor_loss, critic_loss, ent_coef_loss)."""
         c = self.cfg
         with torch.no_grad():
-            a2, logp2 = self.policy(mb.next_observations)
+            a2, logp2, _ = self.policy(mb.next_observations)
             q1n, q2n = self.target(mb.next_observations, a2)
         q1, q2 = self.critic(mb.observations, mb.actions)
         cl = self.loss.critic(q1, q2, q1n, q2n, mb.rewards, mb.dones, ent_coef=ent, logp_next=logp2,
@@ -298,7 +354,10 @@ class SAC:
             self.compare_policy(pl, logp, q1p, q2p, ent)
         self.opt_a.zero_grad(set_to_none=True)
         self.opt_e.zero_grad(set_to_none=True)
-        (pl.actor_loss + pl.ent_coef_loss).backward()       # one backward launch for logp, both q's and log_ent
+        total = pl.actor_loss + pl.ent_coef_loss
+        if smooth is not None:
+            total = total + smooth
+        total.backward()                                    # one backward launch for logp, both q's and log_ent
         self.opt_a.step()
         self.opt_e.step()
         ref = None
@@ -348,18 +407,21 @@ class SAC:
             mb = self.minibatch()
             if self.head_mb is not None:
                 self.head_mb.reset_noise()                  # SAC.train: one matrix per gradient step
-            a_pi, logp = self.policy(mb.observations)
+            a_pi, logp, mean = self.policy(mb.observations)
             ent = self.log_ent.detach().exp()
+            smooth, extra = None, ()
+            if self.caps:
+                smooth, *extra = self.smooth(mb, mean)
             if self.loss is not None:
-                actor_loss, critic_loss, ent_loss = self.kernel_step(mb, a_pi, logp, ent)
-                stats.append(torch.stack((actor_loss, critic_loss, ent.squeeze(), ent_loss)))
+                actor_loss, critic_loss, ent_loss = self.kernel_step(mb, a_pi, logp, ent, smooth)
+                stats.append(torch.stack((actor_loss, critic_loss, ent.squeeze(), ent_loss, *extra)))
                 continue
             ent_loss = -(self.log_ent * (logp.detach() + self.target_entropy)).mean()
             self.opt_e.zero_grad(set_to_none=True)
             ent_loss.backward()
             self.opt_e.step()
             with torch.no_grad():
-                a2, logp2 = self.policy(mb.next_observations)
+                a2, logp2, _ = self.policy(mb.next_observations)
                 q_next = torch.min(*self.target(mb.next_observations, a2)) - ent * logp2[:, None]
                 target = mb.rewards + (1 - mb.dones) * mb.discounts * q_next
             q1, q2 = self.critic(mb.observations, mb.actions)
@@ -370,14 +432,18 @@ class SAC:
             q_pi = torch.min(*self.critic(mb.observations, a_pi))
             actor_loss = (ent * logp[:, None] - q_pi).mean()
             self.opt_a.zero_grad(set_to_none=True)
-            actor_loss.backward()
+            (actor_loss if smooth is None else actor_loss + smooth).backward()
             self.opt_a.step()
             with torch.no_grad():                           # polyak_update
                 for p, t in zip(self.critic.parameters(), self.target.parameters()):
                     t.mul_(1 - c["tau"]).add_(p, alpha=c["tau"])
-            stats.append(torch.stack((actor_loss.detach(), critic_loss.detach(), ent.squeeze(), ent_loss.detach())))
+            stats.append(torch.stack((actor_loss.detach(), critic_loss.detach(), ent.squeeze(), ent_loss.detach(), *extra)))
         s = torch.stack(stats).mean(0).tolist()
         out = {"actor_loss": s[0], "critic_loss": s[1], "ent_coef": s[2], "ent_coef_loss": s[3]}
+        if self.caps:                                       # the regulariser's two terms, unweighted
+            out["caps_temporal"], out["caps_spatial"] = s[4], s[5]
+        if self.check_caps:
+            out["caps_diff"], out["caps_checked"] = self.caps_diff.item(), self.caps_checked
         if self.check_loss:                                 # the largest so far, one read per round
             out["loss_diff"] = dict(zip(("critic", "actor", "ent_coef", "polyak_abs", "polyak_ratio"), self.loss_diff.tolist()))
             out["losses_checked"] = self.losses_checked
@@ -396,17 +462,30 @@ class SAC:
         return {"episodes": eps, "ep_rew_mean": (now[0] - was[0]) / eps, "ep_len_mean": (now[2] - was[2]) / eps}
 
 
+def check_caps_args(caps, caps_kernel, check_caps, n_steps):
+    if caps_kernel and not caps:
+        raise ValueError("caps_kernel routes the CAPS regulariser through DeviceCAPS: it needs caps=True")
+    if check_caps and not caps_kernel:
+        raise ValueError("check_caps compares DeviceCAPS with torch: it needs caps_kernel=True")
+    if caps and n_steps != 1:
+        raise ValueError("caps needs n_steps=1: the temporal term takes the one-step successor, which an n-step "
+                         "sample does not carry")
+
+
 def train(env_id="usv-simple", envs=4096, steps=400, seed=0, log=print, device_replay=True, check_replay=False,
-          max_episode_steps=None, sde_kernel=False, loss_kernel=False, check_loss=False, **cfg):
+          max_episode_steps=None, sde_kernel=False, loss_kernel=False, check_loss=False, caps=False, caps_kernel=False,
+          check_caps=False, **cfg):
     """``steps`` vector steps of ``envs`` envs.  Returns one record per training round (``train_freq``
     steps, then ``gradient_steps`` gradient steps once ``learning_starts`` steps are in the buffer)."""
     import gym_usv_amd
     if check_loss and not loss_kernel:
         raise ValueError("check_loss compares the loss kernels with torch: it needs loss_kernel=True")
+    check_caps_args(caps, caps_kernel, check_caps, dict(CONFIG_SAC, **cfg)["n_steps"])
     kw = {} if max_episode_steps is None else {"max_episode_steps": max_episode_steps}
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False, **kw)
     sac = SAC(env, seed=seed, device_replay=device_replay, check_replay=check_replay, sde_kernel=sde_kernel,
-              loss_kernel=loss_kernel, check_loss=check_loss, **cfg)
+              loss_kernel=loss_kernel, check_loss=check_loss, caps=caps, caps_kernel=caps_kernel, check_caps=check_caps,
+              **cfg)
     c, hist, done_steps = sac.cfg, [], 0
     t0 = time.perf_counter()
     while done_steps < steps:
@@ -441,9 +520,17 @@ def main():
     ap.add_argument("--loss-kernel", action="store_true",
                     help="critic, actor and entropy-coefficient losses and Polyak through DeviceSACLoss / DevicePolyak")
     ap.add_argument("--check-loss", action="store_true", help="with --loss-kernel: also run the torch lines and compare")
+    ap.add_argument("--caps", action="store_true", help="the CAPS regulariser (config_sac's lambda_t, lambda_s, eps_s)")
+    ap.add_argument("--caps-kernel", action="store_true", help="with --caps: through DeviceCAPS instead of torch lines")
+    ap.add_argument("--check-caps", action="store_true", help="with --caps-kernel: also run the torch lines and compare")
+    ap.add_argument("--lambda-t", type=float, default=CONFIG_SAC["lambda_t"])
+    ap.add_argument("--lambda-s", type=float, default=CONFIG_SAC["lambda_s"])
+    ap.add_argument("--eps-s", type=float, default=CONFIG_SAC["eps_s"])
     a = ap.parse_args()
     train(a.env_id, a.envs, a.steps, a.seed, device_replay=a.device_replay, check_replay=a.check_replay,
-          sde_kernel=a.sde_kernel, loss_kernel=a.loss_kernel, check_loss=a.check_loss, buffer_size=a.buffer_size, batch_size=a.batch_size, n_steps=a.n_steps)
+          sde_kernel=a.sde_kernel, loss_kernel=a.loss_kernel, check_loss=a.check_loss, caps=a.caps, caps_kernel=a.caps_kernel,
+          check_caps=a.check_caps, buffer_size=a.buffer_size, batch_size=a.batch_size, n_steps=a.n_steps,
+          lambda_t=a.lambda_t, lambda_s=a.lambda_s, eps_s=a.eps_s)
 
 
 if __name__ == "__main__":

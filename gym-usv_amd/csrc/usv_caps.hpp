@@ -1,0 +1,117 @@
+// usv_caps.hpp -- the CAPS smoothness regulariser as HIP kernels (include/usv_hip.h: usv_caps_perturb /
+// usv_caps_loss): the perturbed observations of the spatial term and the two distance terms with their gradients at
+// unit upstream.  The arithmetic and the summation order are usv_caps_math.hpp's; the backward is sac_scale_kernel.
+//
+//   caps_perturb_kernel
+//       A thread per Philox block: four consecutive elements of one row, the last block of a row cut at W.  A thread
+//       whose four elements are all there and 16-B aligned in both arrays moves them with one 16-B load and one 16-B
+//       store; any other takes them one by one (rows of 715 floats: every fourth row is aligned).  Each thread reads
+//       its elements before it writes them, so out may be obs.
+//   caps_loss_kernel<A>
+//       sac_policy_kernel's shape: a block of 256 threads per partial of 1024 rows, thread t takes rows t, t + 256,
+//       t + 512, t + 768 of the partial with the row's 3 A means in registers, the two distances are its strands' terms,
+//       sac_block_sums and, with more than one partial, sac_combine's ticket hand-off.
+#pragma once
+
+#include "usv_caps_math.hpp"
+#include "usv_sac.hpp"
+
+namespace usv {
+
+struct CapsPerturbArgs {
+  long long blocks;                                  // rows * row_blocks: the threads that have work
+  int W, row_blocks;
+  const float* obs;
+  float* out;
+  float eps;
+  uint64_t seed;
+  uint32_t epoch;
+};
+
+__global__ __launch_bounds__(kBlock) void caps_perturb_kernel(CapsPerturbArgs a) {
+  const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= a.blocks) return;
+  const long long r = t / a.row_blocks;
+  const int b = (int)(t - r * a.row_blocks);
+  const int count = a.W - 4 * b < 4 ? a.W - 4 * b : 4;
+  const long long at = r * a.W + 4 * b;
+  const float* const src = a.obs + at;
+  float* const dst = a.out + at;
+  float z[4];
+  caps_block_normals(a.seed, (uint64_t)r, a.epoch, (uint32_t)b, z);
+  if (count == 4 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+    float4 v = *reinterpret_cast<const float4*>(src);
+    v.x = caps_near(v.x, a.eps, z[0]);
+    v.y = caps_near(v.y, a.eps, z[1]);
+    v.z = caps_near(v.z, a.eps, z[2]);
+    v.w = caps_near(v.w, a.eps, z[3]);
+    *reinterpret_cast<float4*>(dst) = v;
+    return;
+  }
+  float v[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (q < count) v[q] = src[q];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (q < count) dst[q] = caps_near(v[q], a.eps, z[q]);
+}
+
+struct CapsLossArgs {
+  int rows, squash;
+  const float *mean, *mean_next, *mean_near;
+  float lambda_t, lambda_s;
+  float *out3, *g_mean, *g_next, *g_near, *scratch;
+};
+
+template <int A>
+__global__ __launch_bounds__(kBlock) void caps_loss_kernel(CapsLossArgs a) {
+  __shared__ float red[2][kSacWaves];
+  const bool squash = a.squash != 0, grads = a.g_mean || a.g_next || a.g_near;
+  const int64_t base = (int64_t)blockIdx.x * kSacPartialRows;
+  float s[2] = {0.0f, 0.0f};
+#pragma unroll
+  for (int j = 0; j < kSacStrandRows; ++j) {
+    const int64_t i = base + threadIdx.x + j * kSacStrands;
+    if (i < a.rows) {
+      float m[A], mn[A], mr[A], gm[A], gn[A], gr[A];
+#pragma unroll
+      for (int k = 0; k < A; ++k) {
+        m[k] = a.mean[i * A + k];
+        mn[k] = a.mean_next[i * A + k];
+        mr[k] = a.mean_near[i * A + k];
+      }
+      float nT, nS;
+      caps_row<A>(m, mn, mr, squash, a.lambda_t, a.lambda_s, a.rows, nT, nS, grads, gm, gn, gr);
+#pragma unroll
+      for (int k = 0; k < A; ++k) {
+        if (a.g_mean) a.g_mean[i * A + k] = gm[k];
+        if (a.g_next) a.g_next[i * A + k] = gn[k];
+        if (a.g_near) a.g_near[i * A + k] = gr[k];
+      }
+      s[0] = s[0] + nT;
+      s[1] = s[1] + nS;
+    }
+  }
+  sac_block_sums(s, red);
+  if (gridDim.x > 1) {
+    float total[2];
+    if (!sac_combine(s, (int)gridDim.x, a.scratch, total)) return;
+    s[0] = total[0];
+    s[1] = total[1];
+  }
+  if (threadIdx.x == 0) {
+    float out[3];
+    caps_loss(s[0], s[1], a.lambda_t, a.lambda_s, a.rows, out);
+    a.out3[0] = out[0];
+    a.out3[1] = out[1];
+    a.out3[2] = out[2];
+  }
+}
+
+// caps_loss_kernel<A> for A = 1 .. kCapsMaxAct.
+static void (*const kCapsLossKernels[kCapsMaxAct])(CapsLossArgs) = {
+    caps_loss_kernel<1>, caps_loss_kernel<2>, caps_loss_kernel<3>, caps_loss_kernel<4>,
+    caps_loss_kernel<5>, caps_loss_kernel<6>, caps_loss_kernel<7>, caps_loss_kernel<8>};
+
+}  // namespace usv

@@ -33,6 +33,8 @@
 //   usv_sac_math.hpp      SAC update: TD target, losses, unit gradients, the sums' order, Polyak (host C++, no HIP)
 //   usv_sac.hpp           SAC update: fused critic and policy losses, their backward, Polyak over a tensor list
 //                         (usv_sac_critic_loss / _policy_loss / _loss_backward / usv_polyak_update)
+//   usv_caps_math.hpp     CAPS regulariser: counter layout of the perturbation, distances, unit gradients (host C++, no HIP)
+//   usv_caps.hpp          CAPS regulariser: perturbed observations, the fused loss (usv_caps_perturb / usv_caps_loss)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -62,7 +64,8 @@
 #include "usv_rollout_frames.hpp"
 #include "usv_sde.hpp"
 #include "usv_replay.hpp"
-#include "usv_sac.hpp"           // (last: every kernel before it keeps its place in the code object)
+#include "usv_sac.hpp"           // (after the others: every kernel before it keeps its place in the code object)
+#include "usv_caps.hpp"          // (last, for the same reason)
 
 // ============================================================================= host side
 using namespace usv;
@@ -1549,16 +1552,23 @@ int usv_replay_gather_nstep(const usv_replay* rp, int64_t count, const int64_t* 
 }
 
 // ---- fused SAC update (usv_sac.hpp)
-static int sac_bufs(const Buf* b, size_t nb, int& dev) {
+// The buffer check of the loss entries; msg: the refusals for a null buffer, a misaligned one, a first buffer that
+// is no device pointer, another that is none on the first's device.
+static int loss_bufs(const Buf* b, size_t nb, int& dev, const char* const (&msg)[4]) {
   switch (check_bufs(b, nb)) {
-    case kBufNull: return fail(USV_ERR_ARG, "usv_sac: null buffer");
-    case kBufAlign: return fail(USV_ERR_ARG, "usv_sac: scratch is not 16-B aligned or a buffer is not 4-B aligned");
+    case kBufNull: return fail(USV_ERR_ARG, msg[0]);
+    case kBufAlign: return fail(USV_ERR_ARG, msg[1]);
     default: break;
   }
-  if (check_bufs(b, nb, &dev) == kBufDevice)
-    return fail(USV_ERR_ARG, dev < 0 ? "usv_sac: the first buffer is not a device pointer"
-                                     : "usv_sac: a buffer is not a device pointer on the device that holds the first");
+  if (check_bufs(b, nb, &dev) == kBufDevice) return fail(USV_ERR_ARG, dev < 0 ? msg[2] : msg[3]);
   return USV_OK;
+}
+static int sac_bufs(const Buf* b, size_t nb, int& dev) {
+  static const char* const msg[4] = {"usv_sac: null buffer",
+                                     "usv_sac: scratch is not 16-B aligned or a buffer is not 4-B aligned",
+                                     "usv_sac: the first buffer is not a device pointer",
+                                     "usv_sac: a buffer is not a device pointer on the device that holds the first"};
+  return loss_bufs(b, nb, dev, msg);
 }
 
 size_t usv_sac_scratch_floats(int32_t rows) { return rows >= 1 ? sac_scratch_floats(rows) : 0; }
@@ -1688,6 +1698,54 @@ int usv_polyak_update(const usv_polyak_pair* pairs, int32_t n_pairs, void* table
   const PolyakPair* const dp = (const PolyakPair*)table;
   const PolyakChunk* const dc = (const PolyakChunk*)((const char*)table + (size_t)live * sizeof(PolyakPair));
   hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)chunks), dim3(kBlock), 0, (hipStream_t)stream, dp, dc, tau_f, om);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- CAPS regulariser (usv_caps.hpp)
+static int caps_bufs(const Buf* b, size_t nb, int& dev) {
+  static const char* const msg[4] = {"usv_caps: null buffer",
+                                     "usv_caps: scratch is not 16-B aligned or a buffer is not 4-B aligned",
+                                     "usv_caps: the first buffer is not a device pointer",
+                                     "usv_caps: a buffer is not a device pointer on the device that holds the first"};
+  return loss_bufs(b, nb, dev, msg);
+}
+
+int usv_caps_perturb(int32_t rows, int32_t width, const float* obs, float* out, float eps, uint64_t seed, uint32_t epoch,
+                     void* stream) {
+  int dev;
+  if (rows < 1) return fail(USV_ERR_ARG, "usv_caps_perturb: rows must be >= 1");
+  if (width < 1) return fail(USV_ERR_ARG, "usv_caps_perturb: width must be >= 1");
+  if ((int64_t)rows * width > 2147483647) return fail(USV_ERR_ARG, "usv_caps_perturb: rows * width is above 2^31 - 1");
+  if (!caps_weight_ok(eps)) return fail(USV_ERR_ARG, "usv_caps_perturb: eps must be finite and >= 0");
+  const Buf all[] = {{obs, 4}, {out, 4}};
+  if (int rc = caps_bufs(all, 2, dev)) return rc;
+  DeviceGuard g(dev);
+  const int row_blocks = (int)caps_row_blocks(width);
+  const CapsPerturbArgs a{(long long)rows * row_blocks, width, row_blocks, obs, out, eps, seed, epoch};
+  hipLaunchKernelGGL(caps_perturb_kernel, dim3((unsigned)((a.blocks + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_caps_loss(int32_t rows, int32_t act_dim, int32_t squash, const float* mean, const float* mean_next,
+                  const float* mean_near, float lambda_t, float lambda_s, float* out3, float* g_mean, float* g_next,
+                  float* g_near, float* scratch, void* stream) {
+  int dev;
+  if (rows < 1) return fail(USV_ERR_ARG, "usv_caps_loss: rows must be >= 1");
+  if (!caps_act_ok(act_dim)) return fail(USV_ERR_ARG, "usv_caps_loss: act_dim must be in [1, 8]");
+  if ((int64_t)rows * act_dim > 2147483647) return fail(USV_ERR_ARG, "usv_caps_loss: rows * act_dim is above 2^31 - 1");
+  if (!caps_weight_ok(lambda_t)) return fail(USV_ERR_ARG, "usv_caps_loss: lambda_t must be finite and >= 0");
+  if (!caps_weight_ok(lambda_s)) return fail(USV_ERR_ARG, "usv_caps_loss: lambda_s must be finite and >= 0");
+  const Buf all[] = {{scratch, 16}, {mean, 4}, {mean_next, 4}, {mean_near, 4}, {out3, 4},
+                     {g_mean, 4, true}, {g_next, 4, true}, {g_near, 4, true}};
+  if (int rc = caps_bufs(all, 8, dev)) return rc;
+  DeviceGuard g(dev);
+  const CapsLossArgs a{rows, squash != 0, mean, mean_next, mean_near, lambda_t, lambda_s, out3, g_mean, g_next, g_near,
+                       scratch};
+  hipLaunchKernelGGL(kCapsLossKernels[act_dim - 1], dim3((unsigned)sac_partials(rows)), dim3(kBlock), 0,
+                     (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

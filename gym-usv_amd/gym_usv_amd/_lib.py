@@ -200,6 +200,8 @@ SIGNATURES = [
     ("usv_sac_loss_backward", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("usv_polyak_table_bytes", _sz, [ctypes.POINTER(UsvPolyakPair), _i32]),
     ("usv_polyak_update", ctypes.c_int, [ctypes.POINTER(UsvPolyakPair), _i32, _vp, _sz, _i32, ctypes.c_double, _vp]),
+    ("usv_caps_perturb", ctypes.c_int, [_i32, _i32, _vp, _vp, _f32, _u64, _u32, _vp]),
+    ("usv_caps_loss", ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _LIBS = {}
