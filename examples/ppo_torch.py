@@ -42,6 +42,10 @@ this image, so this is a compact PPO with the same hyper-parameters where they c
   torch.  ``--check-eval`` (a test mode) evaluates both heads on every minibatch and records
   ``eval_logp_diff_max``, the largest ``|logp_kernel - logp_torch| / (1 + sum_k (d^2 / s2 + |ln s2|))`` of the
   update, read back once per update.
+* ``--adam-kernel`` (``train(..., adam_kernel=True)``): ``clip_grad_norm_``, ``Adam.step()`` and ``zero_grad`` of every
+  minibatch are ``gym_usv_amd.DeviceAdam``: two HIP launches over the whole parameter list (the norm in a fixed
+  summation order, then clip and Adam in one pass) in place of torch's ops per tensor, with torch's arithmetic up to
+  rounding.  Nothing else changes.
 
 Rollout size at 4096 envs.  config_ppo's ``n_steps=2048, batch_size=64`` are for the reference's 4
 envs: 8 192 samples per update in 128 minibatches.  With 4096 envs the same n_steps would put 8.4 M
@@ -122,7 +126,7 @@ class PPO:
     """Rollout + update over a ``UsvVectorEnv`` (any registered id with a Box action space)."""
 
     def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, frames=False, sde_kernel=False,
-                 eval_kernel=False, check_eval=False, **cfg):
+                 eval_kernel=False, check_eval=False, adam_kernel=False, **cfg):
         from gym_usv_amd.sb3 import DeviceFrameStack
         self.cfg = dict(CONFIG_PPO, **cfg)
         self.env, self.n_steps, self.batch_size = env, n_steps, batch_size
@@ -145,7 +149,12 @@ class PPO:
         torch.manual_seed(seed)
         self.model = ActorCritic(D * self.cfg["n_stack"], A, self.cfg["hidden"], self.cfg["log_std_init"],
                                  self.cfg["use_sde"]).to(self.device)
-        self.opt = torch.optim.Adam(self.model.parameters(), lr=self.cfg["lr"])
+        self.adam_kernel = adam_kernel
+        if adam_kernel:
+            from gym_usv_amd import DeviceAdam
+            self.opt = DeviceAdam(self.model.parameters(), lr=self.cfg["lr"], max_grad_norm=self.cfg["max_grad_norm"])
+        else:
+            self.opt = torch.optim.Adam(self.model.parameters(), lr=self.cfg["lr"])
         lo, hi = env.single_action_space.low, env.single_action_space.high
         self.a_lo = torch.as_tensor(lo, device=self.device, dtype=torch.float32)
         self.a_hi = torch.as_tensor(hi, device=self.device, dtype=torch.float32)
@@ -312,6 +321,13 @@ class PPO:
             rec["eval_logp_diff_max"], self._eval_diff = float(self._eval_diff), None
         return rec
 
+    def gradient_step(self, loss):
+        self.opt.zero_grad(set_to_none=True)
+        loss.backward()
+        if not self.adam_kernel:                        # DeviceAdam.step clips by its max_grad_norm itself
+            nn.utils.clip_grad_norm_(self.model.parameters(), self.cfg["max_grad_norm"])
+        self.opt.step()
+
     def update(self):
         c = self.cfg
         adv, ret = self.advantages()
@@ -332,10 +348,7 @@ class PPO:
                 vl = ((self.model.value(obs[i]) - ret[i]) ** 2).mean()
                 ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
                 loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
-                self.opt.zero_grad(set_to_none=True)
-                loss.backward()
-                nn.utils.clip_grad_norm_(self.model.parameters(), c["max_grad_norm"])
-                self.opt.step()
+                self.gradient_step(loss)
                 stats.append(torch.stack((pg.detach(), vl.detach(), ent.detach())))
         return self.update_record(stats)
 
@@ -354,10 +367,7 @@ class PPO:
                 vl = ((self.model.value(mb.observations) - mb.returns) ** 2).mean()
                 ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
                 loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
-                self.opt.zero_grad(set_to_none=True)
-                loss.backward()
-                nn.utils.clip_grad_norm_(self.model.parameters(), c["max_grad_norm"])
-                self.opt.step()
+                self.gradient_step(loss)
                 stats.append(torch.stack((pg.detach(), vl.detach(), ent.detach())))
         return self.update_record(stats)
 
@@ -381,11 +391,11 @@ class PPO:
 
 
 def train(env_id="usv-simple", envs=4096, updates=10, n_steps=32, batch_size=4096, seed=0, log=print, fused=False,
-          frames=False, sde_kernel=False, eval_kernel=False, check_eval=False, **cfg):
+          frames=False, sde_kernel=False, eval_kernel=False, check_eval=False, adam_kernel=False, **cfg):
     import gym_usv_amd
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False)   # each step is consumed at once
     ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, frames=frames,
-              sde_kernel=sde_kernel, eval_kernel=eval_kernel, check_eval=check_eval, **cfg)
+              sde_kernel=sde_kernel, eval_kernel=eval_kernel, check_eval=check_eval, adam_kernel=adam_kernel, **cfg)
     hist = []
     t0 = time.perf_counter()
     for u in range(updates):
@@ -417,6 +427,8 @@ def main():
                     help="with --sde-kernel: the update's log_prob, ratio and clipped surrogate are DeviceSDE.evaluate")
     ap.add_argument("--check-eval", action="store_true",
                     help="with --sde-kernel: evaluate both heads on every minibatch and record eval_logp_diff_max")
+    ap.add_argument("--adam-kernel", action="store_true",
+                    help="clip_grad_norm_ and Adam.step() of every minibatch through DeviceAdam")
     ap.add_argument("--log", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     if a.frames and not a.fused:
@@ -436,9 +448,11 @@ def main():
         log(json.dumps({"config": {**CONFIG_PPO, "use_sde": not a.no_sde, "env_id": a.env_id, "envs": a.envs,
                                    "n_steps": a.n_steps, "batch_size": a.batch_size, "seed": a.seed,
                                    "fused": a.fused, "frames": a.frames, "sde_kernel": a.sde_kernel,
-                                   "eval_kernel": a.eval_kernel, "check_eval": a.check_eval}}))
+                                   "eval_kernel": a.eval_kernel, "check_eval": a.check_eval,
+                                   "adam_kernel": a.adam_kernel}}))
     train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, fused=a.fused, frames=a.frames,
-          sde_kernel=a.sde_kernel, eval_kernel=a.eval_kernel, check_eval=a.check_eval, use_sde=not a.no_sde)
+          sde_kernel=a.sde_kernel, eval_kernel=a.eval_kernel, check_eval=a.check_eval, adam_kernel=a.adam_kernel,
+          use_sde=not a.no_sde)
 
 
 if __name__ == "__main__":

@@ -50,6 +50,9 @@ is a compact SAC with config_sac's hyper-parameters where they carry over:
   on the kernel's own perturbed observations and records the largest difference of the loss over the loss (read back
   once per round: a test mode).  The temporal term needs the one-step successor: ``caps`` with ``n_steps`` other than 1
   is a ``ValueError``.
+* ``adam_kernel=True`` (``--adam-kernel``): the three optimizers (critic, actor, the one-element ``log_ent``) are
+  ``gym_usv_amd.DeviceAdam``, one HIP launch per ``step()`` over the whole parameter list in place of torch's Adam ops,
+  with torch's arithmetic up to rounding.  Nothing else changes.
 
 ``learning_starts`` counts vector steps here (SB3 counts transitions: 50 000 of them are 12 steps of 4096 envs).  The loop
 collects ``train_freq`` steps, then takes ``gradient_steps`` gradient steps, as SB3's ``learn`` does.
@@ -203,8 +206,8 @@ class TorchReplay:
 
 class SAC:
     def __init__(self, env, seed=0, device_replay=True, check_replay=False, sde_kernel=False, loss_kernel=False,
-                 check_loss=False, caps=False, caps_kernel=False, check_caps=False, **cfg):
-        from gym_usv_amd import DeviceCAPS, DevicePolyak, DeviceReplay, DeviceSACLoss, DeviceSDE
+                 check_loss=False, caps=False, caps_kernel=False, check_caps=False, adam_kernel=False, **cfg):
+        from gym_usv_amd import DeviceAdam, DeviceCAPS, DevicePolyak, DeviceReplay, DeviceSACLoss, DeviceSDE
         from gym_usv_amd.replay import discount_table
         from gym_usv_amd.wrappers import DeviceWrappers
         self.cfg = c = dict(CONFIG_SAC, **cfg)
@@ -218,9 +221,10 @@ class SAC:
         self.target.load_state_dict(self.critic.state_dict())
         self.log_ent = torch.zeros(1, device=d, requires_grad=True)      # ent_coef 'auto': initial value 1
         self.target_entropy = -float(A)
-        self.opt_a = torch.optim.Adam(self.actor.parameters(), lr=c["lr"])
-        self.opt_c = torch.optim.Adam(self.critic.parameters(), lr=c["lr"])
-        self.opt_e = torch.optim.Adam([self.log_ent], lr=c["lr"])
+        adam = DeviceAdam if adam_kernel else torch.optim.Adam      # the same calls either way: zero_grad, step
+        self.opt_a = adam(self.actor.parameters(), lr=c["lr"])
+        self.opt_c = adam(self.critic.parameters(), lr=c["lr"])
+        self.opt_e = adam([self.log_ent], lr=c["lr"])
         lo, hi = env.single_action_space.low, env.single_action_space.high
         self.a_lo = torch.as_tensor(lo, device=d, dtype=torch.float32)
         self.a_hi = torch.as_tensor(hi, device=d, dtype=torch.float32)
@@ -474,7 +478,7 @@ def check_caps_args(caps, caps_kernel, check_caps, n_steps):
 
 def train(env_id="usv-simple", envs=4096, steps=400, seed=0, log=print, device_replay=True, check_replay=False,
           max_episode_steps=None, sde_kernel=False, loss_kernel=False, check_loss=False, caps=False, caps_kernel=False,
-          check_caps=False, **cfg):
+          check_caps=False, adam_kernel=False, **cfg):
     """``steps`` vector steps of ``envs`` envs.  Returns one record per training round (``train_freq``
     steps, then ``gradient_steps`` gradient steps once ``learning_starts`` steps are in the buffer)."""
     import gym_usv_amd
@@ -485,7 +489,7 @@ def train(env_id="usv-simple", envs=4096, steps=400, seed=0, log=print, device_r
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False, **kw)
     sac = SAC(env, seed=seed, device_replay=device_replay, check_replay=check_replay, sde_kernel=sde_kernel,
               loss_kernel=loss_kernel, check_loss=check_loss, caps=caps, caps_kernel=caps_kernel, check_caps=check_caps,
-              **cfg)
+              adam_kernel=adam_kernel, **cfg)
     c, hist, done_steps = sac.cfg, [], 0
     t0 = time.perf_counter()
     while done_steps < steps:
@@ -523,14 +527,15 @@ def main():
     ap.add_argument("--caps", action="store_true", help="the CAPS regulariser (config_sac's lambda_t, lambda_s, eps_s)")
     ap.add_argument("--caps-kernel", action="store_true", help="with --caps: through DeviceCAPS instead of torch lines")
     ap.add_argument("--check-caps", action="store_true", help="with --caps-kernel: also run the torch lines and compare")
+    ap.add_argument("--adam-kernel", action="store_true", help="the three Adam optimizers through DeviceAdam")
     ap.add_argument("--lambda-t", type=float, default=CONFIG_SAC["lambda_t"])
     ap.add_argument("--lambda-s", type=float, default=CONFIG_SAC["lambda_s"])
     ap.add_argument("--eps-s", type=float, default=CONFIG_SAC["eps_s"])
     a = ap.parse_args()
     train(a.env_id, a.envs, a.steps, a.seed, device_replay=a.device_replay, check_replay=a.check_replay,
           sde_kernel=a.sde_kernel, loss_kernel=a.loss_kernel, check_loss=a.check_loss, caps=a.caps, caps_kernel=a.caps_kernel,
-          check_caps=a.check_caps, buffer_size=a.buffer_size, batch_size=a.batch_size, n_steps=a.n_steps,
-          lambda_t=a.lambda_t, lambda_s=a.lambda_s, eps_s=a.eps_s)
+          check_caps=a.check_caps, adam_kernel=a.adam_kernel, buffer_size=a.buffer_size, batch_size=a.batch_size,
+          n_steps=a.n_steps, lambda_t=a.lambda_t, lambda_s=a.lambda_s, eps_s=a.eps_s)
 
 
 if __name__ == "__main__":

@@ -35,6 +35,8 @@
 //                         (usv_sac_critic_loss / _policy_loss / _loss_backward / usv_polyak_update)
 //   usv_caps_math.hpp     CAPS regulariser: counter layout of the perturbation, distances, unit gradients (host C++, no HIP)
 //   usv_caps.hpp          CAPS regulariser: perturbed observations, the fused loss (usv_caps_perturb / usv_caps_loss)
+//   usv_optim_math.hpp    optimizer step: Adam's scalars and element update, the clip, the norm's order (host C++, no HIP)
+//   usv_optim.hpp         optimizer step: clip_grad_norm_ and Adam over a tensor list passed by value (usv_adam_step)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -65,7 +67,8 @@
 #include "usv_sde.hpp"
 #include "usv_replay.hpp"
 #include "usv_sac.hpp"           // (after the others: every kernel before it keeps its place in the code object)
-#include "usv_caps.hpp"          // (last, for the same reason)
+#include "usv_caps.hpp"          // (after usv_sac.hpp, for the same reason)
+#include "usv_optim.hpp"         // (last, for the same reason)
 
 // ============================================================================= host side
 using namespace usv;
@@ -1746,6 +1749,112 @@ int usv_caps_loss(int32_t rows, int32_t act_dim, int32_t squash, const float* me
                        scratch};
   hipLaunchKernelGGL(kCapsLossKernels[act_dim - 1], dim3((unsigned)sac_partials(rows)), dim3(kBlock), 0,
                      (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- fused optimizer step (usv_optim.hpp)
+// The tensors that hold elements, their chunks and their state floats; a refusal's message, or null.  With
+// pointers: they are looked at too.
+static const char* adam_count(const usv_adam_tensor* ts, int32_t n, bool pointers, int64_t& live, int64_t& chunks,
+                              int64_t& state) {
+  live = chunks = state = 0;
+  if (!ts) return "usv_adam_step: null tensors";
+  if (n < 1) return "usv_adam_step: n must be >= 1";
+  for (int32_t i = 0; i < n; ++i) {
+    const usv_adam_tensor& t = ts[i];
+    if (t.numel < 0) return "usv_adam_step: numel must be >= 0";
+    if (t.numel == 0) continue;
+    if (pointers) {
+      if (!t.param || !t.grad) return "usv_adam_step: null param or grad";
+      if (((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad)) & 3) != 0)
+        return "usv_adam_step: param or grad is not 4-B aligned";
+      if (t.param == t.grad) return "usv_adam_step: param and grad are the same address";
+    }
+    ++live;
+    chunks += optim_chunks(t.numel);
+    state += optim_state_floats(t.numel);
+  }
+  if (chunks > 2147483647) return "usv_adam_step: above 2^31 - 1 chunks of 4096 elements";
+  return nullptr;
+}
+
+size_t usv_adam_state_floats(const usv_adam_tensor* tensors, int32_t n) {
+  int64_t live, chunks, state;
+  return adam_count(tensors, n, false, live, chunks, state) ? 0 : (size_t)state;
+}
+
+size_t usv_adam_scratch_floats(const usv_adam_tensor* tensors, int32_t n) {
+  int64_t live, chunks, state;
+  return adam_count(tensors, n, false, live, chunks, state) ? 0 : optim_scratch_floats(chunks);
+}
+
+int usv_adam_step(const usv_adam_tensor* tensors, int32_t n, float* m, float* v, size_t state_floats, int64_t step,
+                  double lr, double beta1, double beta2, double eps, double max_grad_norm, float* scratch,
+                  size_t scratch_floats, float* norm_out, void* stream) {
+  int64_t live, chunks, state;
+  int dev;
+  if (const char* why = adam_count(tensors, n, true, live, chunks, state)) return fail(USV_ERR_ARG, why);
+  if (step < 1) return fail(USV_ERR_ARG, "usv_adam_step: step must be >= 1");
+  if (!adam_rate_ok(lr)) return fail(USV_ERR_ARG, "usv_adam_step: lr must be finite and >= 0");
+  if (!adam_rate_ok(eps)) return fail(USV_ERR_ARG, "usv_adam_step: eps must be finite and >= 0");
+  if (!adam_beta_ok(beta1) || !adam_beta_ok(beta2)) return fail(USV_ERR_ARG, "usv_adam_step: the betas must be in [0, 1)");
+  if (max_grad_norm != max_grad_norm) return fail(USV_ERR_ARG, "usv_adam_step: max_grad_norm is NaN");
+  const bool clip = max_grad_norm >= 0.0;
+  if (clip && !norm_out) return fail(USV_ERR_ARG, "usv_adam_step: clipping needs norm_out");
+  if (!m || !v) return fail(USV_ERR_ARG, "usv_adam_step: null state");
+  if (clip && !scratch) return fail(USV_ERR_ARG, "usv_adam_step: clipping needs scratch");
+  if (state_floats < (size_t)state) return fail(USV_ERR_ARG, "usv_adam_step: the state is too small");
+  if (clip && scratch_floats < optim_scratch_floats(chunks)) return fail(USV_ERR_ARG, "usv_adam_step: the scratch is too small");
+  std::vector<Buf> bufs = {{m, 16}, {v, 16}, {clip ? scratch : nullptr, 16, true}, {clip ? norm_out : nullptr, 4, true}};
+  bufs.reserve(4 + 2 * (size_t)live);
+  for (int32_t i = 0; i < n; ++i)
+    if (tensors[i].numel > 0) {
+      bufs.push_back(Buf{tensors[i].param, 4});
+      bufs.push_back(Buf{tensors[i].grad, 4});
+    }
+  if (check_bufs(bufs.data(), bufs.size()) == kBufAlign)
+    return fail(USV_ERR_ARG, "usv_adam_step: state or scratch is not 16-B aligned or norm_out is not 4-B aligned");
+  if (live == 0) return USV_OK;
+  if (check_bufs(bufs.data(), bufs.size(), &dev) == kBufDevice)
+    return fail(USV_ERR_ARG, dev < 0 ? "usv_adam_step: the state is not a device pointer"
+                                     : "usv_adam_step: a buffer is not a device pointer on the state's device");
+  DeviceGuard g(dev);
+  const AdamScalars sc = adam_scalars(step, lr, beta1, beta2, eps);
+  // one pass: the list in launches of at most kOptimTensors tensors, chunks and state offsets running through
+  auto pass = [&](auto&& launch) {
+    OptimTable tab;
+    int64_t chunk = 0, at = 0;
+    tab.n = 0;
+    for (int32_t i = 0; i <= n; ++i) {
+      if (i < n && tensors[i].numel > 0) {
+        const int k = tab.n++;
+        tab.p[k] = tensors[i].param;
+        tab.g[k] = tensors[i].grad;
+        tab.numel[k] = (long long)tensors[i].numel;
+        tab.state[k] = (long long)at;
+        tab.first[k] = (int)chunk;
+        chunk += optim_chunks(tensors[i].numel);
+        at += optim_state_floats(tensors[i].numel);
+      }
+      if (tab.n == kOptimTensors || (i == n && tab.n > 0)) {
+        tab.first[tab.n] = (int)chunk;
+        launch(tab, dim3((unsigned)(chunk - tab.first[0])));
+        tab.n = 0;
+      }
+    }
+  };
+  if (clip) {
+    pass([&](const OptimTable& tab, dim3 grid) {
+      const OptimSqsumArgs a{tab, (int)chunks, scratch, norm_out};
+      hipLaunchKernelGGL(optim_sqsum_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+    });
+    HIP_TRY(hipGetLastError());
+  }
+  pass([&](const OptimTable& tab, dim3 grid) {
+    const OptimAdamArgs a{tab, m, v, clip ? norm_out : nullptr, (float)max_grad_norm, sc};
+    hipLaunchKernelGGL(optim_adam_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+  });
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

@@ -29,14 +29,17 @@ static_assert(kSacStrands == kBlock && kSacWaves == kWaves, "usv_sac_math.hpp's 
 // every wave's vmcnt(0), the barrier, that lane's release fence and its own wait, a relaxed agent-scope ticket; the
 // last arriver's wave 0 acquires once, and its own later plain loads then see every block's partial: a lane per
 // partial, added in ascending order through readlane.  The ticket word is zero when the caller allocates the
-// scratch, and the last arriver puts it back.
+// scratch, and the last arriver puts it back.  sac_combine_at: the same with the block's partial at `slot` of
+// `partials` and `stride` floats per partial; the tickets may come from several stream-ordered launches that share
+// the scratch (usv_optim.hpp).
 template <int NS>
-__device__ __forceinline__ bool sac_combine(const float (&s)[NS], int partials, float* scratch, float (&total)[NS]) {
+__device__ __forceinline__ bool sac_combine_at(const float (&s)[NS], size_t slot, int partials, int stride,
+                                               float* scratch, float (&total)[NS]) {
   unsigned* const ticket = reinterpret_cast<unsigned*>(scratch);
   float* const part = scratch + kSacScratchHead;
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < NS; ++k) part[(size_t)blockIdx.x * kSacScratchSums + k] = s[k];
+    for (int k = 0; k < NS; ++k) part[slot * stride + k] = s[k];
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -57,7 +60,7 @@ __device__ __forceinline__ bool sac_combine(const float (&s)[NS], int partials, 
     const int p = p0 + (int)threadIdx.x;
     float v[NS];
 #pragma unroll
-    for (int k = 0; k < NS; ++k) v[k] = p < partials ? part[(size_t)p * kSacScratchSums + k] : 0.0f;
+    for (int k = 0; k < NS; ++k) v[k] = p < partials ? part[(size_t)p * stride + k] : 0.0f;
     const int count = partials - p0 < kWave ? partials - p0 : kWave;
     for (int l = 0; l < count; ++l) {
 #pragma unroll
@@ -67,6 +70,11 @@ __device__ __forceinline__ bool sac_combine(const float (&s)[NS], int partials, 
   if (threadIdx.x != 0) return false;
   __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return true;
+}
+
+template <int NS>
+__device__ __forceinline__ bool sac_combine(const float (&s)[NS], int partials, float* scratch, float (&total)[NS]) {
+  return sac_combine_at(s, (size_t)blockIdx.x, partials, kSacScratchSums, scratch, total);
 }
 
 // The block's sums of NS strands each: wave sums by the butterfly, the four of them through LDS.

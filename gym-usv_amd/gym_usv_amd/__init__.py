@@ -19,10 +19,11 @@ from .sde import DeviceSDE, Evaluation, SquashedSample  # noqa: F401
 from .replay import DeviceReplay, NStepReplaySamples, ReplaySamples  # noqa: F401
 from .sac import CriticLoss, DevicePolyak, DeviceSACLoss, PolicyLoss  # noqa: F401
 from .caps import DeviceCAPS, SmoothLoss  # noqa: F401
+from .optim import DeviceAdam  # noqa: F401
 
 __all__ = ["make", "make_vec", "make_sb3_vec_env", "registry", "UsvVectorEnv", "UsvLibError", "ENV_SPECS",
            "DeviceRollout", "DeviceSDE", "DeviceReplay", "ReplaySamples", "NStepReplaySamples",
-           "DeviceSACLoss", "DevicePolyak", "CriticLoss", "PolicyLoss", "DeviceCAPS", "SmoothLoss"]
+           "DeviceSACLoss", "DevicePolyak", "CriticLoss", "PolicyLoss", "DeviceCAPS", "SmoothLoss", "DeviceAdam"]
 
 registry = {k: {"entry_point": f"gym_usv_amd.envs:{cls}", "max_episode_steps": v[1] or None}
             for (k, v), cls in zip(ENV_SPECS.items(), ("UsvSimpleEnv", "UsvSimpleASMCEnv", "UsvAsmcEnv",

@@ -128,6 +128,11 @@ class UsvPolyakPair(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("numel", ctypes.c_int64)]
 
 
+class UsvAdamTensor(ctypes.Structure):
+    """usv_adam_tensor: one (parameter, gradient) tensor of usv_adam_step."""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("numel", ctypes.c_int64)]
+
+
 # (name, restype, argtypes) for every function in include/usv_hip.h
 _vp, _i32, _u64, _sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t
 _i64, _u32, _f32 = ctypes.c_int64, ctypes.c_uint32, ctypes.c_float
@@ -202,6 +207,11 @@ SIGNATURES = [
     ("usv_polyak_update", ctypes.c_int, [ctypes.POINTER(UsvPolyakPair), _i32, _vp, _sz, _i32, ctypes.c_double, _vp]),
     ("usv_caps_perturb", ctypes.c_int, [_i32, _i32, _vp, _vp, _f32, _u64, _u32, _vp]),
     ("usv_caps_loss", ctypes.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_adam_state_floats", _sz, [ctypes.POINTER(UsvAdamTensor), _i32]),
+    ("usv_adam_scratch_floats", _sz, [ctypes.POINTER(UsvAdamTensor), _i32]),
+    ("usv_adam_step", ctypes.c_int, [ctypes.POINTER(UsvAdamTensor), _i32, _vp, _vp, _sz, _i64, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _sz, _vp,
+                                     _vp]),
 ]
 
 _LIBS = {}

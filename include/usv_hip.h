@@ -813,6 +813,46 @@ int usv_caps_loss(int32_t rows, int32_t act_dim, int32_t squash, const float* me
                   float* g_mean, float* g_next, float* g_near /* each [rows, act_dim] or NULL */,
                   float* scratch /* usv_sac_scratch_floats(rows) */, void* stream);
 
+/* ---- Fused optimizer step: torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam.step() (torch 2.x,
+ * amsgrad=False, weight_decay=0, maximize=False, the non-capturable path) over a whole list of tensors: one launch
+ * without clipping, two with it, per 96 tensors of the list (ABI v5 additions).  Handle-free and stream-ordered like
+ * the usv_sac_* entries.  The arithmetic and the fixed summation order are gym-usv_amd/csrc/usv_optim_math.hpp's;
+ * tests/optim_ref.py restates them.
+ *
+ * usv_adam_step, with t = step >= 1 the number of this step (the caller counts), scalars taken in double and cast
+ * once to f32:
+ *   bc1 = 1 - beta1^t;  step_size = lr / bc1;  bc2_sqrt = sqrt(1 - beta2^t)
+ *   with max_grad_norm >= 0:  total = sqrt(sum g^2) over every element of every tensor, written to norm_out[0] (the
+ *     norm before clipping, clip_grad_norm_'s return value);  coef = min(1, max_grad_norm / (total + 1e-6));
+ *     g' = g * coef (always multiplied).  A NaN or inf gradient is not special-cased: an inf gives coef = 0 and NaN
+ *     at that element, as in torch.  With max_grad_norm < 0: no clipping, g' = g, norm_out is not looked at.
+ *   m = m + (g' - m) * (1 - beta1);  v = v * beta2 + ((1 - beta2) * g') * g'
+ *   param = param - step_size * (m / (sqrt(v) / bc2_sqrt + eps))
+ * grad is read and never written: the clipped gradient exists in registers only.  The sum is taken in a fixed order
+ * that depends on the numels alone, so total and every updated value are bitwise reproducible.
+ *
+ * tensors_host is read during the call; tensors with numel == 0 are skipped (their pointers are not looked at).
+ * m, v: the first and second moments, usv_adam_state_floats' worth of floats each, 16-B aligned, zero before step 1:
+ *   the tensors' segments in list order, each padded to a multiple of 4 floats.
+ * scratch: usv_adam_scratch_floats' worth of floats, 16-B aligned, zeroed once when it is allocated (a call leaves
+ *   its first word zero again); needed with clipping only.  Calls that share a scratch must be stream-ordered.
+ * Both size functions return 0 for a list usv_adam_step would refuse by n or numel.
+ * Refused with USV_ERR_ARG before any launch: n < 1, NULL tensors, numel < 0, a NULL or not 4-B aligned param or
+ * grad, param == grad, step < 1, an lr or eps that is NaN, infinite or negative, a beta outside [0, 1), a NaN
+ * max_grad_norm, m, v or (with clipping) scratch that is NULL, not 16-B aligned or too small, clipping without
+ * norm_out, a norm_out that is not 4-B aligned, above 2^31 - 1 chunks of 4096 elements, a buffer that is no device
+ * pointer on the device that holds m. */
+typedef struct usv_adam_tensor {
+  float* param;                /* updated in place */
+  const float* grad;
+  int64_t numel;
+} usv_adam_tensor;
+size_t usv_adam_state_floats(const usv_adam_tensor* tensors_host, int32_t n);
+size_t usv_adam_scratch_floats(const usv_adam_tensor* tensors_host, int32_t n);
+int usv_adam_step(const usv_adam_tensor* tensors_host, int32_t n, float* m, float* v, size_t state_floats, int64_t step,
+                  double lr, double beta1, double beta2, double eps, double max_grad_norm /* < 0: none */,
+                  float* scratch, size_t scratch_floats, float* norm_out, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
