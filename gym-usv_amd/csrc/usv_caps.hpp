@@ -8,9 +8,8 @@
 //       store; any other takes them one by one (rows of 715 floats: every fourth row is aligned).  Each thread reads
 //       its elements before it writes them, so out may be obs.
 //   caps_loss_kernel<A>
-//       sac_policy_kernel's shape: a block of 256 threads per partial of 1024 rows, thread t takes rows t, t + 256,
-//       t + 512, t + 768 of the partial with the row's 3 A means in registers, the two distances are its strands' terms,
-//       sac_block_sums and, with more than one partial, sac_combine's ticket hand-off.
+//       sac_policy_kernel's shape, from the same two forms (usv_sac.hpp): sac_for_rows with the row's 3 A means in
+//       registers and the two distances as the strand's terms, then sac_finish and its thread's write.
 #pragma once
 
 #include "usv_caps_math.hpp"
@@ -66,41 +65,28 @@ struct CapsLossArgs {
 
 template <int A>
 __global__ __launch_bounds__(kBlock) void caps_loss_kernel(CapsLossArgs a) {
-  __shared__ float red[2][kSacWaves];
   const bool squash = a.squash != 0, grads = a.g_mean || a.g_next || a.g_near;
-  const int64_t base = (int64_t)blockIdx.x * kSacPartialRows;
   float s[2] = {0.0f, 0.0f};
+  sac_for_rows(a.rows, [&](int64_t i) {
+    float m[A], mn[A], mr[A], gm[A], gn[A], gr[A];
 #pragma unroll
-  for (int j = 0; j < kSacStrandRows; ++j) {
-    const int64_t i = base + threadIdx.x + j * kSacStrands;
-    if (i < a.rows) {
-      float m[A], mn[A], mr[A], gm[A], gn[A], gr[A];
-#pragma unroll
-      for (int k = 0; k < A; ++k) {
-        m[k] = a.mean[i * A + k];
-        mn[k] = a.mean_next[i * A + k];
-        mr[k] = a.mean_near[i * A + k];
-      }
-      float nT, nS;
-      caps_row<A>(m, mn, mr, squash, a.lambda_t, a.lambda_s, a.rows, nT, nS, grads, gm, gn, gr);
-#pragma unroll
-      for (int k = 0; k < A; ++k) {
-        if (a.g_mean) a.g_mean[i * A + k] = gm[k];
-        if (a.g_next) a.g_next[i * A + k] = gn[k];
-        if (a.g_near) a.g_near[i * A + k] = gr[k];
-      }
-      s[0] = s[0] + nT;
-      s[1] = s[1] + nS;
+    for (int k = 0; k < A; ++k) {
+      m[k] = a.mean[i * A + k];
+      mn[k] = a.mean_next[i * A + k];
+      mr[k] = a.mean_near[i * A + k];
     }
-  }
-  sac_block_sums(s, red);
-  if (gridDim.x > 1) {
-    float total[2];
-    if (!sac_combine(s, (int)gridDim.x, a.scratch, total)) return;
-    s[0] = total[0];
-    s[1] = total[1];
-  }
-  if (threadIdx.x == 0) {
+    float nT, nS;
+    caps_row<A>(m, mn, mr, squash, a.lambda_t, a.lambda_s, a.rows, nT, nS, grads, gm, gn, gr);
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+      if (a.g_mean) a.g_mean[i * A + k] = gm[k];
+      if (a.g_next) a.g_next[i * A + k] = gn[k];
+      if (a.g_near) a.g_near[i * A + k] = gr[k];
+    }
+    s[0] = s[0] + nT;
+    s[1] = s[1] + nS;
+  });
+  if (sac_finish(s, blockIdx.x, (int)gridDim.x, kSacScratchSums, a.scratch)) {
     float out[3];
     caps_loss(s[0], s[1], a.lambda_t, a.lambda_s, a.rows, out);
     a.out3[0] = out[0];

@@ -31,12 +31,14 @@
 //   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather /
 //                         _gather_nstep)
 //   usv_sac_math.hpp      SAC update: TD target, losses, unit gradients, the sums' order, Polyak (host C++, no HIP)
-//   usv_sac.hpp           SAC update: fused critic and policy losses, their backward, Polyak over a tensor list
-//                         (usv_sac_critic_loss / _policy_loss / _loss_backward / usv_polyak_update)
+//   usv_sac.hpp           SAC update: fused critic and policy losses, their backward; the reduction's row loop and
+//                         finish, which usv_caps.hpp and usv_optim.hpp use too
+//                         (usv_sac_critic_loss / _policy_loss / _loss_backward)
 //   usv_caps_math.hpp     CAPS regulariser: counter layout of the perturbation, distances, unit gradients (host C++, no HIP)
 //   usv_caps.hpp          CAPS regulariser: perturbed observations, the fused loss (usv_caps_perturb / usv_caps_loss)
 //   usv_optim_math.hpp    optimizer step: Adam's scalars and element update, the clip, the norm's order (host C++, no HIP)
-//   usv_optim.hpp         optimizer step: clip_grad_norm_ and Adam over a tensor list passed by value (usv_adam_step)
+//   usv_optim.hpp         kernels over a tensor list: clip_grad_norm_ and Adam (the list passed by value), Polyak (a
+//                         device table), one element loop under both (usv_adam_step / usv_polyak_update)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -897,6 +899,39 @@ static BufFault check_bufs(const Buf* b, size_t n, int* dev = nullptr) {
 }
 static BufFault check_bufs(Bufs b) { return check_bufs(b.begin(), b.size()); }
 
+// The refusal of check_bufs's fault, or USV_OK: the one chain of every trainer entry.  msg: for a null buffer, a
+// misaligned one, a first buffer that is no device pointer, another that is none on the first's device; without dev
+// the last two are not looked for.
+using BufMsgs = const char* const (&)[4];
+static int refuse_bufs(const Buf* b, size_t n, int* dev, BufMsgs msg) {
+  switch (check_bufs(b, n, dev)) {
+    case kBufNull: return fail(USV_ERR_ARG, msg[0]);
+    case kBufAlign: return fail(USV_ERR_ARG, msg[1]);
+    case kBufDevice: return fail(USV_ERR_ARG, *dev < 0 ? msg[2] : msg[3]);
+    case kBufOk: break;
+  }
+  return USV_OK;
+}
+// ... with the messages of the entries that name no buffer but their 16-B one: `prefix` and `wide`.
+static int refuse_bufs(const Buf* b, size_t n, int& dev, const char* prefix, const char* wide) {
+  const std::string p = std::string(prefix) + ": ", first = p + "the first buffer is not a device pointer",
+                    null = p + "null buffer", align = p + wide + " is not 16-B aligned or a buffer is not 4-B aligned",
+                    other = p + "a buffer is not a device pointer on the device that holds the first";
+  const char* const msg[4] = {null.c_str(), align.c_str(), first.c_str(), other.c_str()};
+  return refuse_bufs(b, n, &dev, msg);
+}
+
+// The gathers' check of idx and of their outputs out[0 .. n), before the buffers' device is looked at.
+static int refuse_gather_bufs(const char* fn, const int64_t* idx, const Buf* out, size_t n) {
+  const std::string p = std::string(fn) + ": ";
+  if (!idx) return fail(USV_ERR_ARG, p + "null idx");
+  const BufFault of = check_bufs(out, n);
+  if (of == kBufNull) return fail(USV_ERR_ARG, p + "null output");
+  if ((reinterpret_cast<uintptr_t>(idx) & 7) != 0) return fail(USV_ERR_ARG, p + "idx is not 8-B aligned");
+  if (of == kBufAlign) return fail(USV_ERR_ARG, p + "an output is not 4-B aligned");
+  return USV_OK;
+}
+
 // The launch geometry of the kernels whose waves own kWrapEnvs envs each.
 static dim3 wrap_grid(int n) { return dim3((n + kWaves * kWrapEnvs - 1) / (kWaves * kWrapEnvs)); }
 
@@ -927,14 +962,10 @@ static int wrap_args(const usv_wrap* w, const usv_norm* zn, int64_t j, Bufs more
   size_t nb = 7;
   for (const Buf& b : more) all[nb++] = b;
   if (zn) nb += norm_bufs(zn, all + nb);
-  switch (check_bufs(all, nb, &dev)) {
-    case kBufNull: return fail(USV_ERR_ARG, "usv_wrap: null argument");
-    case kBufAlign: return fail(USV_ERR_ARG, "usv_wrap: a buffer is not aligned to its element size");
-    case kBufDevice:
-      return fail(USV_ERR_ARG, dev < 0 ? "usv_wrap: ring is not a device pointer"
-                                       : "usv_wrap: a buffer is not a device pointer on the ring's device");
-    case kBufOk: break;
-  }
+  if (int rc = refuse_bufs(all, nb, &dev, {"usv_wrap: null argument", "usv_wrap: a buffer is not aligned to its element size",
+                                          "usv_wrap: ring is not a device pointer",
+                                          "usv_wrap: a buffer is not a device pointer on the ring's device"}))
+    return rc;
   const int k = w->n_stack;
   a = WrapArgs{w->n, w->obs_dim, k, w->reward_bytes, wrap_slot(j, k), wrap_mirror_slot(j, k),
                wrap_terminal_slot(j, k), (w->flags & USV_WRAP_CLEAR_KEEPS_SIGN) != 0, wrap_ring_stride(w->obs_dim, k), w->ring,
@@ -1098,14 +1129,11 @@ static int rollout_args(const usv_rollout* ro, bool in_range, Bufs more, RoArgs&
   size_t nb = 12;
   if (check_bufs(all, nb) == kBufNull) return fail(USV_ERR_ARG, "usv_rollout: null buffer");
   for (const Buf& b : more) all[nb++] = b;
-  switch (check_bufs(all, nb, &dev)) {
-    case kBufNull: return fail(USV_ERR_ARG, "usv_rollout: null argument");
-    case kBufAlign: return fail(USV_ERR_ARG, "usv_rollout: a buffer is not aligned to its element size");
-    case kBufDevice:
-      return fail(USV_ERR_ARG, dev < 0 ? "usv_rollout: obs is not a device pointer"
-                                       : "usv_rollout: a buffer is not a device pointer on the device that holds obs");
-    case kBufOk: break;
-  }
+  if (int rc = refuse_bufs(all, nb, &dev,
+                           {"usv_rollout: null argument", "usv_rollout: a buffer is not aligned to its element size",
+                            "usv_rollout: obs is not a device pointer",
+                            "usv_rollout: a buffer is not a device pointer on the device that holds obs"}))
+    return rc;
   long long* const totals = (long long*)ro->scratch;
   a = RoArgs{ro->n, ro->n_steps, ro->obs_width, ro->act_dim, ro->term_cap, ro->obs, ro->act, ro->rew, ro->val,
              ro->logp, ro->adv, ro->ret, ro->start, ro->term_slot, ro->term_obs, ro->term_count, totals,
@@ -1219,13 +1247,9 @@ int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, cons
   if (int rc = rollout_frames_check(ro, fr)) return rc;
   if (B <= 0) return fail(USV_ERR_ARG, "usv_rollout_gather: B must be > 0");
   if (!fr->bad_count) return fail(USV_ERR_ARG, "usv_rollout_gather: null bad_count");
-  if (!idx) return fail(USV_ERR_ARG, "usv_rollout_gather: null idx");
   const Bufs more = {{idx, 8},     {fr->bad_count, 4}, {obs_out, 4}, {act_out, 4},
                      {val_out, 4}, {logp_out, 4},      {adv_out, 4}, {ret_out, 4}};
-  const BufFault of = check_bufs(more.begin() + 2, 6);  // the outputs
-  if (of == kBufNull) return fail(USV_ERR_ARG, "usv_rollout_gather: null output");
-  if ((reinterpret_cast<uintptr_t>(idx) & 7) != 0) return fail(USV_ERR_ARG, "usv_rollout_gather: idx is not 8-B aligned");
-  if (of == kBufAlign) return fail(USV_ERR_ARG, "usv_rollout_gather: an output is not 4-B aligned");
+  if (int rc = refuse_gather_bufs("usv_rollout_gather", idx, more.begin() + 2, 6)) return rc;
   usv_rollout r = *ro;
   if (fr->frames) r.obs = fr->frames;
   if (int rc = rollout_args(&r, true, more, a, dev)) return rc;
@@ -1272,17 +1296,7 @@ static int sde_stride(const usv_sde* s, size_t stride, const char* fn, const cha
   return fail(USV_ERR_ARG, std::string(fn) + ": the " + what + "row stride must be a multiple of 4 and >= latent_dim");
 }
 
-static int sde_bufs(const Buf* b, size_t nb, int& dev) {
-  switch (check_bufs(b, nb)) {
-    case kBufNull: return fail(USV_ERR_ARG, "usv_sde: null buffer");
-    case kBufAlign: return fail(USV_ERR_ARG, "usv_sde: lat is not 16-B aligned or a buffer is not 4-B aligned");
-    default: break;
-  }
-  if (check_bufs(b, nb, &dev) == kBufDevice)
-    return fail(USV_ERR_ARG, dev < 0 ? "usv_sde: the first buffer is not a device pointer"
-                                     : "usv_sde: a buffer is not a device pointer on the device that holds the first");
-  return USV_OK;
-}
+static int sde_bufs(const Buf* b, size_t nb, int& dev) { return refuse_bufs(b, nb, dev, "usv_sde", "lat"); }
 
 static size_t sde_scratch_floats(int64_t rows, const usv_sde* s) {
   return (size_t)sde_partials(rows) * (size_t)s->latent_dim * (size_t)s->act_dim;
@@ -1439,20 +1453,15 @@ static int replay_args(const usv_replay* rp, Bufs more, RpArgs& a, int& dev) {
   Buf all[kMaxBufs] = {{rp->frames, 4}, {rp->next_frame, 4}, {rp->act, 4},     {rp->rew, 4},      {rp->done, 1},
                        {rp->timeout, 1}, {rp->age, 1},       {rp->age_now, 1}, {rp->bad_count, 4}};
   size_t nb = 9;
-  switch (check_bufs(all, nb)) {
-    case kBufNull: return fail(USV_ERR_ARG, "usv_replay: null buffer");
-    case kBufAlign: return fail(USV_ERR_ARG, "usv_replay: a buffer is not aligned to its element size");
-    default: break;
-  }
+  if (int rc = refuse_bufs(all, nb, nullptr,
+                           {"usv_replay: null buffer", "usv_replay: a buffer is not aligned to its element size"}))
+    return rc;
   for (const Buf& b : more) all[nb++] = b;
-  switch (check_bufs(all, nb, &dev)) {
-    case kBufNull: return fail(USV_ERR_ARG, "usv_replay: null argument");
-    case kBufAlign: return fail(USV_ERR_ARG, "usv_replay: an argument is not aligned to its element size");
-    case kBufDevice:
-      return fail(USV_ERR_ARG, dev < 0 ? "usv_replay: frames is not a device pointer"
-                                       : "usv_replay: a buffer is not a device pointer on the device that holds frames");
-    case kBufOk: break;
-  }
+  if (int rc = refuse_bufs(all, nb, &dev,
+                           {"usv_replay: null argument", "usv_replay: an argument is not aligned to its element size",
+                            "usv_replay: frames is not a device pointer",
+                            "usv_replay: a buffer is not a device pointer on the device that holds frames"}))
+    return rc;
   a = RpArgs{rp->n, rp->rows, rp->obs_width, rp->act_dim, rp->k, rp->d, rp->flags & USV_REPLAY_CLEAR_KEEPS_SIGN,
              (int)rp_frame_rows(rp->rows, rp->k), rp->frames, rp->next_frame, rp->act, rp->rew, rp->done, rp->timeout,
              rp->age, rp->age_now, rp->bad_count};
@@ -1500,79 +1509,59 @@ int usv_replay_put_step(const usv_replay* rp, int64_t c, const void* rew, int32_
   return USV_OK;
 }
 
-int usv_replay_gather(const usv_replay* rp, int64_t count, const int64_t* idx, int32_t B, float* obs_out, float* act_out,
-                      float* next_obs_out, float* done_out, float* rew_out, void* stream) {
+// usv_replay_gather (fn names it; n_steps, table and discount_out are not looked at) and, with nstep,
+// usv_replay_gather_nstep.
+static int replay_gather(const char* fn, bool nstep, const usv_replay* rp, int64_t count, const int64_t* idx, int32_t B,
+                         int32_t n_steps, const float* table, float* obs_out, float* act_out, float* next_obs_out,
+                         float* done_out, float* rew_out, float* discount_out, void* stream) {
   RpArgs a;
   int dev;
-  if (count < 0) return fail(USV_ERR_ARG, "usv_replay_gather: count must be >= 0");
-  if (B <= 0) return fail(USV_ERR_ARG, "usv_replay_gather: B must be > 0");
-  if (!idx) return fail(USV_ERR_ARG, "usv_replay_gather: null idx");
-  const Bufs more = {{idx, 8}, {obs_out, 4}, {act_out, 4}, {next_obs_out, 4}, {done_out, 4}, {rew_out, 4}};
-  const BufFault of = check_bufs(more.begin() + 1, 5);  // the outputs
-  if (of == kBufNull) return fail(USV_ERR_ARG, "usv_replay_gather: null output");
-  if ((reinterpret_cast<uintptr_t>(idx) & 7) != 0) return fail(USV_ERR_ARG, "usv_replay_gather: idx is not 8-B aligned");
-  if (of == kBufAlign) return fail(USV_ERR_ARG, "usv_replay_gather: an output is not 4-B aligned");
+  const std::string p = std::string(fn) + ": ";
+  if (count < 0) return fail(USV_ERR_ARG, p + "count must be >= 0");
+  if (B <= 0) return fail(USV_ERR_ARG, p + "B must be > 0");
+  RpDiscounts tab = {};
+  if (nstep) {
+    if (n_steps < 1 || n_steps > kRpMaxNStep) return fail(USV_ERR_ARG, p + "n_steps must be in [1, 32]");
+    if (!table) return fail(USV_ERR_ARG, p + "null discount table");
+    for (int j = 0; j <= n_steps; ++j) {
+      if (!std::isfinite(table[j])) return fail(USV_ERR_ARG, p + "a discount table entry is not finite");
+      tab.g[j] = table[j];
+    }
+  }
+  const Bufs more = {{idx, 8},      {obs_out, 4}, {act_out, 4},           {next_obs_out, 4},
+                     {done_out, 4}, {rew_out, 4}, {discount_out, 4, !nstep}};
+  if (int rc = refuse_gather_bufs(fn, idx, more.begin() + 1, 6)) return rc;
   if (int rc = replay_args(rp, more, a, dev)) return rc;
   DeviceGuard g(dev);
   const int per_block = kWaves * kRpRows;
   const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
-  hipLaunchKernelGGL(replay_gather_kernel, grid, block, 0, (hipStream_t)stream, a, rp_laps(count, a.R, a.k),
-                     (long long)rp_size(count, a.R), idx, (int)B, obs_out, act_out, next_obs_out, done_out, rew_out);
+  const RpLaps laps = rp_laps(count, a.R, a.k);
+  const long long size = rp_size(count, a.R);
+  if (nstep)
+    hipLaunchKernelGGL(replay_gather_nstep_kernel, grid, block, 0, (hipStream_t)stream, a, laps, size, idx, (int)B,
+                       (int)n_steps, tab, obs_out, act_out, next_obs_out, done_out, rew_out, discount_out);
+  else
+    hipLaunchKernelGGL(replay_gather_kernel, grid, block, 0, (hipStream_t)stream, a, laps, size, idx, (int)B, obs_out,
+                       act_out, next_obs_out, done_out, rew_out);
   HIP_TRY(hipGetLastError());
   return USV_OK;
+}
+
+int usv_replay_gather(const usv_replay* rp, int64_t count, const int64_t* idx, int32_t B, float* obs_out, float* act_out,
+                      float* next_obs_out, float* done_out, float* rew_out, void* stream) {
+  return replay_gather("usv_replay_gather", false, rp, count, idx, B, 0, nullptr, obs_out, act_out, next_obs_out,
+                       done_out, rew_out, nullptr, stream);
 }
 
 int usv_replay_gather_nstep(const usv_replay* rp, int64_t count, const int64_t* idx, int32_t B, int32_t n_steps,
                             const float* table, float* obs_out, float* act_out, float* next_obs_out, float* done_out,
                             float* rew_out, float* discount_out, void* stream) {
-  RpArgs a;
-  int dev;
-  if (count < 0) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: count must be >= 0");
-  if (B <= 0) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: B must be > 0");
-  if (n_steps < 1 || n_steps > kRpMaxNStep) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: n_steps must be in [1, 32]");
-  if (!table) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: null discount table");
-  RpDiscounts tab = {};
-  for (int j = 0; j <= n_steps; ++j) {
-    if (!std::isfinite(table[j])) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: a discount table entry is not finite");
-    tab.g[j] = table[j];
-  }
-  if (!idx) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: null idx");
-  const Bufs more = {{idx, 8},      {obs_out, 4}, {act_out, 4},     {next_obs_out, 4},
-                     {done_out, 4}, {rew_out, 4}, {discount_out, 4}};
-  const BufFault of = check_bufs(more.begin() + 1, 6);  // the outputs
-  if (of == kBufNull) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: null output");
-  if ((reinterpret_cast<uintptr_t>(idx) & 7) != 0) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: idx is not 8-B aligned");
-  if (of == kBufAlign) return fail(USV_ERR_ARG, "usv_replay_gather_nstep: an output is not 4-B aligned");
-  if (int rc = replay_args(rp, more, a, dev)) return rc;
-  DeviceGuard g(dev);
-  const int per_block = kWaves * kRpRows;
-  const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
-  hipLaunchKernelGGL(replay_gather_nstep_kernel, grid, block, 0, (hipStream_t)stream, a, rp_laps(count, a.R, a.k),
-                     (long long)rp_size(count, a.R), idx, (int)B, (int)n_steps, tab, obs_out, act_out, next_obs_out,
-                     done_out, rew_out, discount_out);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
+  return replay_gather("usv_replay_gather_nstep", true, rp, count, idx, B, n_steps, table, obs_out, act_out,
+                       next_obs_out, done_out, rew_out, discount_out, stream);
 }
 
 // ---- fused SAC update (usv_sac.hpp)
-// The buffer check of the loss entries; msg: the refusals for a null buffer, a misaligned one, a first buffer that
-// is no device pointer, another that is none on the first's device.
-static int loss_bufs(const Buf* b, size_t nb, int& dev, const char* const (&msg)[4]) {
-  switch (check_bufs(b, nb)) {
-    case kBufNull: return fail(USV_ERR_ARG, msg[0]);
-    case kBufAlign: return fail(USV_ERR_ARG, msg[1]);
-    default: break;
-  }
-  if (check_bufs(b, nb, &dev) == kBufDevice) return fail(USV_ERR_ARG, dev < 0 ? msg[2] : msg[3]);
-  return USV_OK;
-}
-static int sac_bufs(const Buf* b, size_t nb, int& dev) {
-  static const char* const msg[4] = {"usv_sac: null buffer",
-                                     "usv_sac: scratch is not 16-B aligned or a buffer is not 4-B aligned",
-                                     "usv_sac: the first buffer is not a device pointer",
-                                     "usv_sac: a buffer is not a device pointer on the device that holds the first"};
-  return loss_bufs(b, nb, dev, msg);
-}
+static int sac_bufs(const Buf* b, size_t nb, int& dev) { return refuse_bufs(b, nb, dev, "usv_sac", "scratch"); }
 
 size_t usv_sac_scratch_floats(int32_t rows) { return rows >= 1 ? sac_scratch_floats(rows) : 0; }
 
@@ -1631,88 +1620,8 @@ int usv_sac_loss_backward(int32_t rows, const float* up, const float* g1, const 
   return USV_OK;
 }
 
-// The pairs that hold elements and their chunks; a refusal's message, or null.
-static const char* polyak_count(const usv_polyak_pair* pairs, int32_t n, int64_t& live, int64_t& chunks) {
-  live = chunks = 0;
-  if (!pairs) return "usv_polyak_update: null pairs";
-  if (n < 1) return "usv_polyak_update: n_pairs must be >= 1";
-  for (int32_t i = 0; i < n; ++i) {
-    const usv_polyak_pair& p = pairs[i];
-    if (p.numel < 0) return "usv_polyak_update: numel must be >= 0";
-    if (p.numel == 0) continue;
-    if (!p.src || !p.dst) return "usv_polyak_update: null src or dst";
-    if (((reinterpret_cast<uintptr_t>(p.src) | reinterpret_cast<uintptr_t>(p.dst)) & 3) != 0)
-      return "usv_polyak_update: src or dst is not 4-B aligned";
-    if (p.src == p.dst) return "usv_polyak_update: src and dst are the same address";
-    ++live;
-    chunks += polyak_chunks(p.numel);
-  }
-  if (chunks > 2147483647) return "usv_polyak_update: above 2^31 - 1 chunks of 4096 elements";
-  return nullptr;
-}
-static size_t polyak_bytes(int64_t live, int64_t chunks) {
-  return (size_t)live * sizeof(PolyakPair) + (size_t)chunks * sizeof(PolyakChunk);
-}
-
-size_t usv_polyak_table_bytes(const usv_polyak_pair* pairs, int32_t n_pairs) {
-  int64_t live, chunks;
-  return polyak_count(pairs, n_pairs, live, chunks) ? 0 : polyak_bytes(live, chunks);
-}
-
-int usv_polyak_update(const usv_polyak_pair* pairs, int32_t n_pairs, void* table, size_t table_bytes, int32_t upload,
-                      double tau, void* stream) {
-  int64_t live, chunks;
-  int dev;
-  if (const char* why = polyak_count(pairs, n_pairs, live, chunks)) return fail(USV_ERR_ARG, why);
-  if (!polyak_tau_ok(tau)) return fail(USV_ERR_ARG, "usv_polyak_update: tau must be in [0, 1]");
-  if (live == 0) return USV_OK;
-  if (!table) return fail(USV_ERR_ARG, "usv_polyak_update: null table");
-  if ((reinterpret_cast<uintptr_t>(table) & 7) != 0) return fail(USV_ERR_ARG, "usv_polyak_update: the table is not 8-B aligned");
-  if (table_bytes < polyak_bytes(live, chunks)) return fail(USV_ERR_ARG, "usv_polyak_update: the table is too small");
-  std::vector<Buf> bufs = {{table, 8}};
-  if (upload)
-    for (int32_t i = 0; i < n_pairs; ++i)
-      if (pairs[i].numel > 0) {
-        bufs.push_back(Buf{pairs[i].src, 4});
-        bufs.push_back(Buf{pairs[i].dst, 4});
-      }
-  if (check_bufs(bufs.data(), bufs.size(), &dev) == kBufDevice)
-    return fail(USV_ERR_ARG, dev < 0 ? "usv_polyak_update: the table is not a device pointer"
-                                     : "usv_polyak_update: a tensor is not a device pointer on the table's device");
-  DeviceGuard g(dev);
-  static_assert(sizeof(PolyakPair) == 24 && sizeof(PolyakChunk) == 8, "the table's layout");
-  if (upload) {
-    std::vector<unsigned char> host(polyak_bytes(live, chunks));
-    PolyakPair* const hp = reinterpret_cast<PolyakPair*>(host.data());
-    PolyakChunk* const hc = reinterpret_cast<PolyakChunk*>(host.data() + (size_t)live * sizeof(PolyakPair));
-    int64_t at = 0, c = 0;
-    for (int32_t i = 0; i < n_pairs; ++i) {
-      if (pairs[i].numel == 0) continue;
-      hp[at] = PolyakPair{pairs[i].src, pairs[i].dst, (long long)pairs[i].numel};
-      for (int64_t k = 0; k < polyak_chunks(pairs[i].numel); ++k) hc[c++] = PolyakChunk{(int)at, (int)k};
-      ++at;
-    }
-    HIP_TRY(hipDeviceSynchronize());                 // launches in flight may read the old table
-    HIP_TRY(hipMemcpy(table, host.data(), host.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-  }
-  float tau_f, om;
-  polyak_coeffs(tau, tau_f, om);
-  const PolyakPair* const dp = (const PolyakPair*)table;
-  const PolyakChunk* const dc = (const PolyakChunk*)((const char*)table + (size_t)live * sizeof(PolyakPair));
-  hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)chunks), dim3(kBlock), 0, (hipStream_t)stream, dp, dc, tau_f, om);
-  HIP_TRY(hipGetLastError());
-  return USV_OK;
-}
-
 // ---- CAPS regulariser (usv_caps.hpp)
-static int caps_bufs(const Buf* b, size_t nb, int& dev) {
-  static const char* const msg[4] = {"usv_caps: null buffer",
-                                     "usv_caps: scratch is not 16-B aligned or a buffer is not 4-B aligned",
-                                     "usv_caps: the first buffer is not a device pointer",
-                                     "usv_caps: a buffer is not a device pointer on the device that holds the first"};
-  return loss_bufs(b, nb, dev, msg);
-}
+static int caps_bufs(const Buf* b, size_t nb, int& dev) { return refuse_bufs(b, nb, dev, "usv_caps", "scratch"); }
 
 int usv_caps_perturb(int32_t rows, int32_t width, const float* obs, float* out, float eps, uint64_t seed, uint32_t epoch,
                      void* stream) {
@@ -1753,40 +1662,147 @@ int usv_caps_loss(int32_t rows, int32_t act_dim, int32_t squash, const float* me
   return USV_OK;
 }
 
-// ---- fused optimizer step (usv_optim.hpp)
-// The tensors that hold elements, their chunks and their state floats; a refusal's message, or null.  With
+// ---- kernels over a tensor list (usv_optim.hpp): Polyak's pairs and Adam's tensors behind one walk
+// One tensor of either list, as the table has it: what the kernels write, what they read.
+struct ListItem {
+  float* p;
+  const float* g;
+  int64_t numel;
+};
+static ListItem list_item(const usv_polyak_pair& x) { return {x.dst, x.src, x.numel}; }
+static ListItem list_item(const usv_adam_tensor& x) { return {x.param, x.grad, x.numel}; }
+
+// The words of an entry's refusals: its name, its list, the list's length and its struct's two pointers.
+struct ListWords {
+  const char *fn, *list, *n, *a, *b;
+};
+static const ListWords kPolyakWords = {"usv_polyak_update","pairs", "n_pairs", "src", "dst"};
+static const ListWords kAdamWords = {"usv_adam_step", "tensors", "n", "param", "grad"};
+
+extern "C++" {
+// The tensors that hold elements, their chunks and their state floats; a refusal's message, or none.  With
 // pointers: they are looked at too.
-static const char* adam_count(const usv_adam_tensor* ts, int32_t n, bool pointers, int64_t& live, int64_t& chunks,
+template <class T>
+static std::string list_count(const ListWords& w, const T* ts, int32_t n, bool pointers, int64_t& live, int64_t& chunks,
                               int64_t& state) {
+  const std::string p = std::string(w.fn) + ": ", ab = std::string(w.a) + " or " + w.b;
   live = chunks = state = 0;
-  if (!ts) return "usv_adam_step: null tensors";
-  if (n < 1) return "usv_adam_step: n must be >= 1";
+  if (!ts) return p + "null " + w.list;
+  if (n < 1) return p + w.n + " must be >= 1";
   for (int32_t i = 0; i < n; ++i) {
-    const usv_adam_tensor& t = ts[i];
-    if (t.numel < 0) return "usv_adam_step: numel must be >= 0";
+    const ListItem t = list_item(ts[i]);
+    if (t.numel < 0) return p + "numel must be >= 0";
     if (t.numel == 0) continue;
     if (pointers) {
-      if (!t.param || !t.grad) return "usv_adam_step: null param or grad";
-      if (((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad)) & 3) != 0)
-        return "usv_adam_step: param or grad is not 4-B aligned";
-      if (t.param == t.grad) return "usv_adam_step: param and grad are the same address";
+      if (!t.p || !t.g) return p + "null " + ab;
+      if (((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g)) & 3) != 0) return p + ab + " is not 4-B aligned";
+      if (t.p == t.g) return p + w.a + " and " + w.b + " are the same address";
     }
     ++live;
     chunks += optim_chunks(t.numel);
     state += optim_state_floats(t.numel);
   }
-  if (chunks > 2147483647) return "usv_adam_step: above 2^31 - 1 chunks of 4096 elements";
-  return nullptr;
+  if (chunks > 2147483647) return p + "above 2^31 - 1 chunks of 4096 elements";
+  return {};
+}
+
+// The pointers of the tensors that hold elements, behind those already in bufs.
+template <class T>
+static void list_bufs(const T* ts, int32_t n, std::vector<Buf>& bufs) {
+  for (int32_t i = 0; i < n; ++i)
+    if (const ListItem t = list_item(ts[i]); t.numel > 0) {
+      bufs.push_back(Buf{t.p, 4});
+      bufs.push_back(Buf{t.g, 4});
+    }
+}
+
+// One pass: launch(tab, grid) for the list in launches of at most kTableTensors tensors, chunks and state offsets
+// running through.
+template <class T, class L>
+static void list_pass(const T* ts, int32_t n, L&& launch) {
+  TensorTable tab;
+  int64_t chunk = 0, at = 0;
+  tab.n = 0;
+  for (int32_t i = 0; i <= n; ++i) {
+    if (i < n && ts[i].numel > 0) {
+      const ListItem t = list_item(ts[i]);
+      const int k = tab.n++;
+      tab.p[k] = t.p;
+      tab.g[k] = t.g;
+      tab.numel[k] = (long long)t.numel;
+      tab.state[k] = (long long)at;
+      tab.first[k] = (int)chunk;
+      chunk += optim_chunks(t.numel);
+      at += optim_state_floats(t.numel);
+    }
+    if (tab.n == kTableTensors || (i == n && tab.n > 0)) {
+      tab.first[tab.n] = (int)chunk;
+      launch(tab, dim3((unsigned)(chunk - tab.first[0])));
+      tab.n = 0;
+    }
+  }
+}
+}  // extern "C++"
+
+static size_t polyak_bytes(int64_t live, int64_t chunks) {
+  return (size_t)live * sizeof(PolyakPair) + (size_t)chunks * sizeof(PolyakChunk);
+}
+
+size_t usv_polyak_table_bytes(const usv_polyak_pair* pairs, int32_t n_pairs) {
+  int64_t live, chunks, state;
+  return list_count(kPolyakWords, pairs, n_pairs, true, live, chunks, state).empty() ? polyak_bytes(live, chunks) : 0;
+}
+
+int usv_polyak_update(const usv_polyak_pair* pairs, int32_t n_pairs, void* table, size_t table_bytes, int32_t upload,
+                      double tau, void* stream) {
+  int64_t live, chunks, state;
+  int dev;
+  if (const std::string why = list_count(kPolyakWords, pairs, n_pairs, true, live, chunks, state); !why.empty())
+    return fail(USV_ERR_ARG, why);
+  if (!polyak_tau_ok(tau)) return fail(USV_ERR_ARG, "usv_polyak_update: tau must be in [0, 1]");
+  if (live == 0) return USV_OK;
+  if (!table) return fail(USV_ERR_ARG, "usv_polyak_update: null table");
+  if ((reinterpret_cast<uintptr_t>(table) & 7) != 0) return fail(USV_ERR_ARG, "usv_polyak_update: the table is not 8-B aligned");
+  if (table_bytes < polyak_bytes(live, chunks)) return fail(USV_ERR_ARG, "usv_polyak_update: the table is too small");
+  std::vector<Buf> bufs = {{table, 8}};
+  if (upload) list_bufs(pairs, n_pairs, bufs);
+  if (check_bufs(bufs.data(), bufs.size(), &dev) == kBufDevice)
+    return fail(USV_ERR_ARG, dev < 0 ? "usv_polyak_update: the table is not a device pointer"
+                                     : "usv_polyak_update: a tensor is not a device pointer on the table's device");
+  DeviceGuard g(dev);
+  static_assert(sizeof(PolyakPair) == 24 && sizeof(PolyakChunk) == 8, "the table's layout");
+  if (upload) {
+    std::vector<unsigned char> host(polyak_bytes(live, chunks));
+    PolyakPair* const hp = reinterpret_cast<PolyakPair*>(host.data());
+    PolyakChunk* const hc = reinterpret_cast<PolyakChunk*>(host.data() + (size_t)live * sizeof(PolyakPair));
+    int64_t at = 0, c = 0;
+    for (int32_t i = 0; i < n_pairs; ++i) {
+      if (pairs[i].numel == 0) continue;
+      hp[at] = PolyakPair{pairs[i].src, pairs[i].dst, (long long)pairs[i].numel};
+      for (int64_t k = 0; k < polyak_chunks(pairs[i].numel); ++k) hc[c++] = PolyakChunk{(int)at, (int)k};
+      ++at;
+    }
+    HIP_TRY(hipDeviceSynchronize());                 // launches in flight may read the old table
+    HIP_TRY(hipMemcpy(table, host.data(), host.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  float tau_f, om;
+  polyak_coeffs(tau, tau_f, om);
+  const PolyakPair* const dp = (const PolyakPair*)table;
+  const PolyakChunk* const dc = (const PolyakChunk*)((const char*)table + (size_t)live * sizeof(PolyakPair));
+  hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)chunks), dim3(kBlock), 0, (hipStream_t)stream, dp, dc, tau_f, om);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
 }
 
 size_t usv_adam_state_floats(const usv_adam_tensor* tensors, int32_t n) {
   int64_t live, chunks, state;
-  return adam_count(tensors, n, false, live, chunks, state) ? 0 : (size_t)state;
+  return list_count(kAdamWords, tensors, n, false, live, chunks, state).empty() ? (size_t)state : 0;
 }
 
 size_t usv_adam_scratch_floats(const usv_adam_tensor* tensors, int32_t n) {
   int64_t live, chunks, state;
-  return adam_count(tensors, n, false, live, chunks, state) ? 0 : optim_scratch_floats(chunks);
+  return list_count(kAdamWords, tensors, n, false, live, chunks, state).empty() ? optim_scratch_floats(chunks) : 0;
 }
 
 int usv_adam_step(const usv_adam_tensor* tensors, int32_t n, float* m, float* v, size_t state_floats, int64_t step,
@@ -1794,7 +1810,8 @@ int usv_adam_step(const usv_adam_tensor* tensors, int32_t n, float* m, float* v,
                   size_t scratch_floats, float* norm_out, void* stream) {
   int64_t live, chunks, state;
   int dev;
-  if (const char* why = adam_count(tensors, n, true, live, chunks, state)) return fail(USV_ERR_ARG, why);
+  if (const std::string why = list_count(kAdamWords, tensors, n, true, live, chunks, state); !why.empty())
+    return fail(USV_ERR_ARG, why);
   if (step < 1) return fail(USV_ERR_ARG, "usv_adam_step: step must be >= 1");
   if (!adam_rate_ok(lr)) return fail(USV_ERR_ARG, "usv_adam_step: lr must be finite and >= 0");
   if (!adam_rate_ok(eps)) return fail(USV_ERR_ARG, "usv_adam_step: eps must be finite and >= 0");
@@ -1808,50 +1825,24 @@ int usv_adam_step(const usv_adam_tensor* tensors, int32_t n, float* m, float* v,
   if (clip && scratch_floats < optim_scratch_floats(chunks)) return fail(USV_ERR_ARG, "usv_adam_step: the scratch is too small");
   std::vector<Buf> bufs = {{m, 16}, {v, 16}, {clip ? scratch : nullptr, 16, true}, {clip ? norm_out : nullptr, 4, true}};
   bufs.reserve(4 + 2 * (size_t)live);
-  for (int32_t i = 0; i < n; ++i)
-    if (tensors[i].numel > 0) {
-      bufs.push_back(Buf{tensors[i].param, 4});
-      bufs.push_back(Buf{tensors[i].grad, 4});
-    }
-  if (check_bufs(bufs.data(), bufs.size()) == kBufAlign)
-    return fail(USV_ERR_ARG, "usv_adam_step: state or scratch is not 16-B aligned or norm_out is not 4-B aligned");
+  list_bufs(tensors, n, bufs);
+  static const char* const msg[4] = {"usv_adam_step: null state",
+                                     "usv_adam_step: state or scratch is not 16-B aligned or norm_out is not 4-B aligned",
+                                     "usv_adam_step: the state is not a device pointer",
+                                     "usv_adam_step: a buffer is not a device pointer on the state's device"};
+  if (int rc = refuse_bufs(bufs.data(), bufs.size(), nullptr, msg)) return rc;
   if (live == 0) return USV_OK;
-  if (check_bufs(bufs.data(), bufs.size(), &dev) == kBufDevice)
-    return fail(USV_ERR_ARG, dev < 0 ? "usv_adam_step: the state is not a device pointer"
-                                     : "usv_adam_step: a buffer is not a device pointer on the state's device");
+  if (int rc = refuse_bufs(bufs.data(), bufs.size(), &dev, msg)) return rc;
   DeviceGuard g(dev);
   const AdamScalars sc = adam_scalars(step, lr, beta1, beta2, eps);
-  // one pass: the list in launches of at most kOptimTensors tensors, chunks and state offsets running through
-  auto pass = [&](auto&& launch) {
-    OptimTable tab;
-    int64_t chunk = 0, at = 0;
-    tab.n = 0;
-    for (int32_t i = 0; i <= n; ++i) {
-      if (i < n && tensors[i].numel > 0) {
-        const int k = tab.n++;
-        tab.p[k] = tensors[i].param;
-        tab.g[k] = tensors[i].grad;
-        tab.numel[k] = (long long)tensors[i].numel;
-        tab.state[k] = (long long)at;
-        tab.first[k] = (int)chunk;
-        chunk += optim_chunks(tensors[i].numel);
-        at += optim_state_floats(tensors[i].numel);
-      }
-      if (tab.n == kOptimTensors || (i == n && tab.n > 0)) {
-        tab.first[tab.n] = (int)chunk;
-        launch(tab, dim3((unsigned)(chunk - tab.first[0])));
-        tab.n = 0;
-      }
-    }
-  };
   if (clip) {
-    pass([&](const OptimTable& tab, dim3 grid) {
+    list_pass(tensors, n, [&](const TensorTable& tab, dim3 grid) {
       const OptimSqsumArgs a{tab, (int)chunks, scratch, norm_out};
       hipLaunchKernelGGL(optim_sqsum_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
     });
     HIP_TRY(hipGetLastError());
   }
-  pass([&](const OptimTable& tab, dim3 grid) {
+  list_pass(tensors, n, [&](const TensorTable& tab, dim3 grid) {
     const OptimAdamArgs a{tab, m, v, clip ? norm_out : nullptr, (float)max_grad_norm, sc};
     hipLaunchKernelGGL(optim_adam_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
   });

@@ -1,21 +1,28 @@
-// usv_optim.hpp -- the fused optimizer step as HIP kernels (include/usv_hip.h: usv_adam_step): torch's
-// clip_grad_norm_ and Adam.step() over a whole parameter list, one launch without clipping and two with it.  The
-// arithmetic and the summation order are usv_optim_math.hpp's.
+// usv_optim.hpp -- the kernels over a list of tensors (include/usv_hip.h: usv_adam_step, usv_polyak_update): torch's
+// clip_grad_norm_ and Adam.step() over a whole parameter list, one launch without clipping and two with it, and SB3's
+// polyak_update over a list of pairs, one launch.  The arithmetic and the summation order are usv_optim_math.hpp's;
+// Polyak's arithmetic is usv_sac_math.hpp's.
 //
-// The tensor table travels by value in the kernel arguments (OptimTable, at most kOptimTensors tensors a launch; a
-// longer list takes more launches per pass): a gradient made after zero_grad(set_to_none=True) has a new address on
+// Adam's tensor table travels by value in the kernel arguments (TensorTable, at most kTableTensors tensors a launch;
+// a longer list takes more launches per pass): a gradient made after zero_grad(set_to_none=True) has a new address on
 // every backward, and a device table would have to be uploaded, with a synchronise, on every step.  A block owns one
-// chunk of C = 4096 elements and finds its tensor by a binary search over the wave-uniform chunk starts.
+// chunk of C = 4096 elements and finds its tensor by a binary search over the wave-uniform chunk starts (table_find).
+// Polyak's pairs rarely move, and its kernel is short enough for the 3.5 KB of arguments to show (3.7 against 3.3 us
+// queued): it keeps a device table, uploaded when an address has changed.
+// chunk_elements is the element loop of optim_adam_kernel and polyak_kernel: 16-B accesses where the caller says the
+// chunk's pointers are 16-B aligned, 4-B accesses for the tail of numel % 4 and for misaligned tensors.
 //
 //   optim_sqsum_kernel   the chunk's sum of squares: thread t is strand t, a 16-B load per group where the chunk's
 //                        gradient pointer is 16-B aligned and four 4-B loads where it is not, the same groups either
-//                        way.  Block sums by sac_block_sums; the chunk's sum goes to the scratch at its global chunk
-//                        number and the block that draws the last ticket of the whole list, over all launches of the
-//                        pass, adds the chunk sums in ascending order and writes the norm (sac_combine_at).  No block
-//                        waits for another.
+//                        way.  sac_finish (usv_sac.hpp) with the chunk's sum at its global chunk number: the block
+//                        that draws the last ticket of the whole list, over all launches of the pass, adds the chunk
+//                        sums in ascending order, and its thread writes the norm.  No block waits for another.
 //   optim_adam_kernel    coef from the norm (with clipping), then one read each of p, g, m, v and one write each of
-//                        p, m, v per element: 16-B accesses where p and g are both 16-B aligned, 4-B accesses for the
-//                        tail of numel % 4 and for misaligned tensors.  The state segments are always 16-B aligned.
+//                        p, m, v per element, wide where p and g are both 16-B aligned.  The state segments are
+//                        always 16-B aligned.
+//   polyak_kernel        a block per chunk of one tensor pair, found through the device table of pairs and the table
+//                        of (pair, chunk) per block: one read of src and dst and one write of dst per element, wide
+//                        where both are 16-B aligned.
 #pragma once
 
 #include "usv_optim_math.hpp"
@@ -24,35 +31,46 @@ namespace usv {
 
 static_assert(kOptimStrands == kBlock, "usv_optim_math.hpp's strands are this block's threads");
 
-constexpr int kOptimTensors = 96;                    // K
+constexpr int kTableTensors = 96;                    // K
 
-struct OptimTable {
-  float* p[kOptimTensors];
-  const float* g[kOptimTensors];
-  long long numel[kOptimTensors];
-  long long state[kOptimTensors];                    // the segment's offset in m and v, floats
-  int first[kOptimTensors + 1];                      // global number of the tensor's first chunk; [n]: the launch's end
+struct TensorTable {
+  float* p[kTableTensors];                           // written: Adam's parameter, Polyak's dst
+  const float* g[kTableTensors];                     // read: Adam's gradient, Polyak's src
+  long long numel[kTableTensors];
+  long long state[kTableTensors];                    // the segment's offset in m and v, floats (Adam alone)
+  int first[kTableTensors + 1];                      // global number of the tensor's first chunk; [n]: the launch's end
   int n;
 };
 
 struct OptimSqsumArgs {
-  OptimTable tab;
+  TensorTable tab;
   int chunks;                                        // of the whole list: the ticket's target
   float *scratch, *norm_out;
 };
 
 struct OptimAdamArgs {
-  OptimTable tab;
+  TensorTable tab;
   float *m, *v;
   const float* total;                                // the norm, or null without clipping
   float max_norm;
   AdamScalars s;
 };
+
 static_assert(sizeof(OptimSqsumArgs) <= 3584 && sizeof(OptimAdamArgs) <= 3584,
               "the arguments and the hidden ones stay under HIP's 4 KiB");
 
+// Polyak's device table: the pairs that hold elements, then a (pair, chunk) per block.
+struct PolyakPair {
+  const float* src;
+  float* dst;
+  long long numel;
+};
+struct PolyakChunk {
+  int pair, chunk;
+};
+
 // The block's chunk: its tensor's slot in the table, its offset in the tensor and its element count.
-__device__ __forceinline__ int optim_find(const OptimTable& tab, long long& off, int& count) {
+__device__ __forceinline__ int table_find(const TensorTable& tab, long long& off, int& count) {
   const int chunk = tab.first[0] + (int)blockIdx.x;
   int lo = 0, hi = tab.n;                            // first[lo] <= chunk < first[hi]
   while (hi - lo > 1) {
@@ -65,11 +83,55 @@ __device__ __forceinline__ int optim_find(const OptimTable& tab, long long& off,
   return lo;
 }
 
+template <int W>
+struct alignas(4 * W) FloatPack {                    // what one access moves
+  float v[W];
+};
+
+// The element loop of a chunk of `count` elements: f(x, y) for every element, x its values in the arrays rw (written
+// back) and y those in ro.  wide: every pointer is 16-B aligned, and whole groups of four go by 16-B accesses.
+template <int NW, int NR, class F>
+__device__ __forceinline__ void chunk_elements(float* const (&rw)[NW], const float* const (&ro)[NR], int count, bool wide,
+                                               F&& f) {
+  auto at = [&](int i, auto pack) {
+    using V = decltype(pack);
+    constexpr int W = sizeof(V) / sizeof(float);
+    V x[NW], y[NR];
+#pragma unroll
+    for (int n = 0; n < NW; ++n) x[n] = reinterpret_cast<const V*>(rw[n])[i];
+#pragma unroll
+    for (int n = 0; n < NR; ++n) y[n] = reinterpret_cast<const V*>(ro[n])[i];
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      float xe[NW], ye[NR];
+#pragma unroll
+      for (int n = 0; n < NW; ++n) xe[n] = x[n].v[k];
+#pragma unroll
+      for (int n = 0; n < NR; ++n) ye[n] = y[n].v[k];
+      f(xe, ye);
+#pragma unroll
+      for (int n = 0; n < NW; ++n) x[n].v[k] = xe[n];
+    }
+#pragma unroll
+    for (int n = 0; n < NW; ++n) reinterpret_cast<V*>(rw[n])[i] = x[n];
+  };
+  int done = 0;
+  if (wide) {
+    const int n4 = count / 4;
+    for (int i = threadIdx.x; i < n4; i += kBlock) at(i, FloatPack<4>{});
+    done = 4 * n4;
+  }
+  for (int i = done + threadIdx.x; i < count; i += kBlock) at(i, FloatPack<1>{});
+}
+
+__device__ __forceinline__ bool both_wide(const void* a, const void* b) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+
 __global__ __launch_bounds__(kBlock) void optim_sqsum_kernel(OptimSqsumArgs a) {
-  __shared__ float red[1][kSacWaves];
   long long off;
   int count;
-  const int t = optim_find(a.tab, off, count);
+  const int t = table_find(a.tab, off, count);
   const float* const g = a.tab.g[t] + off;
   float s[1] = {0.0f};
   if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
@@ -87,58 +149,35 @@ __global__ __launch_bounds__(kBlock) void optim_sqsum_kernel(OptimSqsumArgs a) {
   } else {
     s[0] = optim_strand_sqsum(g, count, (int)threadIdx.x);
   }
-  sac_block_sums(s, red);
-  if (a.chunks > 1) {
-    float total[1];
-    if (!sac_combine_at(s, (size_t)(a.tab.first[0] + (int)blockIdx.x), a.chunks, 1, a.scratch, total)) return;
-    s[0] = total[0];
-  }
-  if (threadIdx.x == 0) a.norm_out[0] = optim_norm(s[0]);
+  if (sac_finish(s, (size_t)(a.tab.first[0] + (int)blockIdx.x), a.chunks, 1, a.scratch)) a.norm_out[0] = optim_norm(s[0]);
 }
 
 __global__ __launch_bounds__(kBlock) void optim_adam_kernel(OptimAdamArgs a) {
   long long off;
   int count;
-  const int t = optim_find(a.tab, off, count);
+  const int t = table_find(a.tab, off, count);
   const bool clip = a.total != nullptr;
   const float coef = clip ? adam_clip_coef(a.total[0], a.max_norm) : 1.0f;
   float* const p = a.tab.p[t] + off;
   const float* const g = a.tab.g[t] + off;
-  float* const m = a.m + a.tab.state[t] + off;
-  float* const v = a.v + a.tab.state[t] + off;
   const AdamScalars s = a.s;
-  int done = 0;
-  if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g)) & 15) == 0) {
-    const int n4 = count / 4;
-    for (int i = threadIdx.x; i < n4; i += kBlock) {
-      float4 pp = reinterpret_cast<float4*>(p)[i];
-      float4 gg = reinterpret_cast<const float4*>(g)[i];
-      float4 mm = reinterpret_cast<float4*>(m)[i];
-      float4 vv = reinterpret_cast<float4*>(v)[i];
-      if (clip) {
-        gg.x = adam_clipped(gg.x, coef);
-        gg.y = adam_clipped(gg.y, coef);
-        gg.z = adam_clipped(gg.z, coef);
-        gg.w = adam_clipped(gg.w, coef);
-      }
-      adam_value(pp.x, mm.x, vv.x, gg.x, s);
-      adam_value(pp.y, mm.y, vv.y, gg.y, s);
-      adam_value(pp.z, mm.z, vv.z, gg.z, s);
-      adam_value(pp.w, mm.w, vv.w, gg.w, s);
-      reinterpret_cast<float4*>(p)[i] = pp;
-      reinterpret_cast<float4*>(m)[i] = mm;
-      reinterpret_cast<float4*>(v)[i] = vv;
-    }
-    done = 4 * n4;
-  }
-  for (int i = done + threadIdx.x; i < count; i += kBlock) {
-    float pp = p[i], mm = m[i], vv = v[i];
-    const float gg = clip ? adam_clipped(g[i], coef) : g[i];
-    adam_value(pp, mm, vv, gg, s);
-    p[i] = pp;
-    m[i] = mm;
-    v[i] = vv;
-  }
+  chunk_elements({p, a.m + a.tab.state[t] + off, a.v + a.tab.state[t] + off}, {g}, count, both_wide(p, g),
+                 [&](float (&x)[3], const float (&y)[1]) {
+                   adam_value(x[0], x[1], x[2], clip ? adam_clipped(y[0], coef) : y[0], s);
+                 });
+}
+
+__global__ __launch_bounds__(kBlock) void polyak_kernel(const PolyakPair* __restrict__ pairs,
+                                                        const PolyakChunk* __restrict__ chunks, float tau_f, float om) {
+  const PolyakChunk c = chunks[blockIdx.x];
+  const PolyakPair pr = pairs[c.pair];
+  const long long off = (long long)c.chunk * kPolyakChunk;
+  const long long left = pr.numel - off;
+  const int count = left < kPolyakChunk ? (int)left : kPolyakChunk;
+  float* const dst = pr.dst + off;
+  const float* const src = pr.src + off;
+  chunk_elements({dst}, {src}, count, both_wide(dst, src),
+                 [&](float (&x)[1], const float (&y)[1]) { x[0] = polyak_value(x[0], y[0], tau_f, om); });
 }
 
 }  // namespace usv

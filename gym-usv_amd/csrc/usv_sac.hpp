@@ -1,20 +1,22 @@
 // usv_sac.hpp -- the fused SAC update as HIP kernels (include/usv_hip.h: usv_sac_critic_loss / _policy_loss /
-// _loss_backward / usv_polyak_update): SB3's SAC.train lines for the TD target, the twin-critic loss, the actor and
-// entropy-coefficient losses with their gradients at unit upstream, and polyak_update over a list of tensors.
-// The arithmetic and the summation order are usv_sac_math.hpp's.
+// _loss_backward): SB3's SAC.train lines for the TD target, the twin-critic loss, the actor and
+// entropy-coefficient losses with their gradients at unit upstream.  The arithmetic and the summation order are
+// usv_sac_math.hpp's.  (polyak_update over a list of tensors is usv_optim.hpp's, next to the element loop it shares.)
+//
+// The reduction that these kernels, caps_loss_kernel (usv_caps.hpp) and optim_sqsum_kernel (usv_optim.hpp) share has
+// two forms and no other: sac_for_rows, a thread's rows of its partial, and sac_finish, from the strands' sums to the
+// one thread that holds the totals.
 //
 //   sac_critic_kernel, sac_policy_kernel
 //       A block of 256 threads per partial of P = 1024 rows.  Thread t takes rows t, t + 256, t + 512, t + 768 of its
-//       partial: every row stream is read with coalesced 4-B loads, the per-row outputs are written the same way,
-//       and the thread's terms are its strand.  The strands are reduced by the DPP butterfly (sde_wave_sum) and the
-//       four wave sums through LDS.  One partial: thread 0 writes the loss.  More: thread 0 stores the block's sums
-//       to the caller's scratch and draws a ticket; the block that draws the last one adds all partials in ascending
-//       order and writes the loss (sac_combine).  No block waits for another.
+//       partial (sac_for_rows): every row stream is read with coalesced 4-B loads, the per-row outputs are written
+//       the same way, and the thread's terms are its strand.  sac_finish: the strands are reduced by the DPP
+//       butterfly (sde_wave_sum) and the four wave sums through LDS.  One partial: thread 0 has the sums.  More:
+//       thread 0 stores the block's sums to the caller's scratch and draws a ticket; the block that draws the last
+//       one adds all partials in ascending order (sac_combine_at).  No block waits for another.  The thread that
+//       sac_finish names writes the loss.
 //   sac_scale_kernel   the backward of either loss: the saved unit gradients times the upstream scalars, read on
 //                      the device; a null upstream writes zeros.
-//   polyak_kernel      a block per chunk of C = 4096 elements of one tensor pair, found through a device table of
-//                      pairs and a table of (pair, chunk) per block: 16-B accesses where both of the chunk's pointers
-//                      are 16-B aligned, 4-B accesses otherwise.
 #pragma once
 
 #include "usv_sac_math.hpp"
@@ -29,9 +31,9 @@ static_assert(kSacStrands == kBlock && kSacWaves == kWaves, "usv_sac_math.hpp's 
 // every wave's vmcnt(0), the barrier, that lane's release fence and its own wait, a relaxed agent-scope ticket; the
 // last arriver's wave 0 acquires once, and its own later plain loads then see every block's partial: a lane per
 // partial, added in ascending order through readlane.  The ticket word is zero when the caller allocates the
-// scratch, and the last arriver puts it back.  sac_combine_at: the same with the block's partial at `slot` of
-// `partials` and `stride` floats per partial; the tickets may come from several stream-ordered launches that share
-// the scratch (usv_optim.hpp).
+// scratch, and the last arriver puts it back.  The block's partial is at `slot` of `partials`, `stride` floats per
+// partial; the tickets may come from several stream-ordered launches that share the scratch (usv_optim.hpp).
+// sac_finish is its only caller.
 template <int NS>
 __device__ __forceinline__ bool sac_combine_at(const float (&s)[NS], size_t slot, int partials, int stride,
                                                float* scratch, float (&total)[NS]) {
@@ -72,11 +74,6 @@ __device__ __forceinline__ bool sac_combine_at(const float (&s)[NS], size_t slot
   return true;
 }
 
-template <int NS>
-__device__ __forceinline__ bool sac_combine(const float (&s)[NS], int partials, float* scratch, float (&total)[NS]) {
-  return sac_combine_at(s, (size_t)blockIdx.x, partials, kSacScratchSums, scratch, total);
-}
-
 // The block's sums of NS strands each: wave sums by the butterfly, the four of them through LDS.
 template <int NS>
 __device__ __forceinline__ void sac_block_sums(float (&s)[NS], float (&red)[NS][kSacWaves]) {
@@ -91,6 +88,34 @@ __device__ __forceinline__ void sac_block_sums(float (&s)[NS], float (&red)[NS][
   for (int k = 0; k < NS; ++k) s[k] = sac_waves_sum(red[k]);
 }
 
+// The finish of a reduction, called by every thread of the block with its strand's sums s: the block's sums and,
+// with more than one partial, the hand-off (the block's partial goes to `slot`).  True in the one thread of the grid
+// that holds the totals, left in s.
+template <int NS>
+__device__ __forceinline__ bool sac_finish(float (&s)[NS], size_t slot, int partials, int stride, float* scratch) {
+  __shared__ float red[NS][kSacWaves];
+  sac_block_sums(s, red);
+  if (partials > 1) {
+    float total[NS];
+    if (!sac_combine_at(s, slot, partials, stride, scratch, total)) return false;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) s[k] = total[k];
+  }
+  return threadIdx.x == 0;
+}
+
+// The row loop: row(i) for the thread's rows i < rows of the block's partial, strand t's rows t, t + 256, t + 512,
+// t + 768 of it.
+template <class F>
+__device__ __forceinline__ void sac_for_rows(int rows, F&& row) {
+  const int64_t base = (int64_t)blockIdx.x * kSacPartialRows;
+#pragma unroll
+  for (int j = 0; j < kSacStrandRows; ++j) {
+    const int64_t i = base + threadIdx.x + j * kSacStrands;
+    if (i < rows) row(i);
+  }
+}
+
 struct SacCriticArgs {
   int rows;
   const float *q1, *q2, *q1t, *q2t, *rew, *done, *ent, *logp_next, *disc;
@@ -99,34 +124,21 @@ struct SacCriticArgs {
 };
 
 __global__ __launch_bounds__(kBlock) void sac_critic_kernel(SacCriticArgs a) {
-  __shared__ float red[2][kSacWaves];
   const bool with_ent = a.ent != nullptr;
   const float ent = with_ent ? a.ent[0] : 0.0f;
-  const int64_t base = (int64_t)blockIdx.x * kSacPartialRows;
   float s[2] = {0.0f, 0.0f};
-#pragma unroll
-  for (int j = 0; j < kSacStrandRows; ++j) {
-    const int64_t i = base + threadIdx.x + j * kSacStrands;
-    if (i < a.rows) {
-      const float tgt = sac_target(a.q1t[i], a.q2t[i], with_ent, ent, with_ent ? a.logp_next[i] : 0.0f, a.rew[i],
-                                   a.done[i], a.disc ? a.disc[i] : a.gamma);
-      float t1, t2, g1, g2;
-      sac_critic_row(a.q1[i], a.q2[i], tgt, a.rows, t1, t2, g1, g2);
-      a.tgt[i] = tgt;
-      if (a.g_q1) a.g_q1[i] = g1;
-      if (a.g_q2) a.g_q2[i] = g2;
-      s[0] = s[0] + t1;
-      s[1] = s[1] + t2;
-    }
-  }
-  sac_block_sums(s, red);
-  if (gridDim.x > 1) {
-    float total[2];
-    if (!sac_combine(s, (int)gridDim.x, a.scratch, total)) return;
-    s[0] = total[0];
-    s[1] = total[1];
-  }
-  if (threadIdx.x == 0) a.loss[0] = sac_critic_loss(s[0], s[1], a.rows);
+  sac_for_rows(a.rows, [&](int64_t i) {
+    const float tgt = sac_target(a.q1t[i], a.q2t[i], with_ent, ent, with_ent ? a.logp_next[i] : 0.0f, a.rew[i],
+                                 a.done[i], a.disc ? a.disc[i] : a.gamma);
+    float t1, t2, g1, g2;
+    sac_critic_row(a.q1[i], a.q2[i], tgt, a.rows, t1, t2, g1, g2);
+    a.tgt[i] = tgt;
+    if (a.g_q1) a.g_q1[i] = g1;
+    if (a.g_q2) a.g_q2[i] = g2;
+    s[0] = s[0] + t1;
+    s[1] = s[1] + t2;
+  });
+  if (sac_finish(s, blockIdx.x, (int)gridDim.x, kSacScratchSums, a.scratch)) a.loss[0] = sac_critic_loss(s[0], s[1], a.rows);
 }
 
 struct SacPolicyArgs {
@@ -137,36 +149,22 @@ struct SacPolicyArgs {
 };
 
 __global__ __launch_bounds__(kBlock) void sac_policy_kernel(SacPolicyArgs a) {
-  __shared__ float red[3][kSacWaves];
   const float ent = a.ent[0];
   const bool with_le = a.log_ent != nullptr;
   const float le = with_le ? a.log_ent[0] : 0.0f;
   const float g_logp = sac_mean(ent, a.rows);
-  const int64_t base = (int64_t)blockIdx.x * kSacPartialRows;
   float s[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int j = 0; j < kSacStrandRows; ++j) {
-    const int64_t i = base + threadIdx.x + j * kSacStrands;
-    if (i < a.rows) {
-      float ta, tl, tg, g1, g2;
-      sac_policy_row(a.logp[i], a.q1[i], a.q2[i], ent, le, a.te, a.rows, ta, tl, tg, g1, g2);
-      if (a.g_logp) a.g_logp[i] = g_logp;
-      if (a.g_q1) a.g_q1[i] = g1;
-      if (a.g_q2) a.g_q2[i] = g2;
-      s[0] = s[0] + ta;
-      s[1] = s[1] + tl;
-      s[2] = s[2] + tg;
-    }
-  }
-  sac_block_sums(s, red);
-  if (gridDim.x > 1) {
-    float total[3];
-    if (!sac_combine(s, (int)gridDim.x, a.scratch, total)) return;
-    s[0] = total[0];
-    s[1] = total[1];
-    s[2] = total[2];
-  }
-  if (threadIdx.x == 0) {
+  sac_for_rows(a.rows, [&](int64_t i) {
+    float ta, tl, tg, g1, g2;
+    sac_policy_row(a.logp[i], a.q1[i], a.q2[i], ent, le, a.te, a.rows, ta, tl, tg, g1, g2);
+    if (a.g_logp) a.g_logp[i] = g_logp;
+    if (a.g_q1) a.g_q1[i] = g1;
+    if (a.g_q2) a.g_q2[i] = g2;
+    s[0] = s[0] + ta;
+    s[1] = s[1] + tl;
+    s[2] = s[2] + tg;
+  });
+  if (sac_finish(s, blockIdx.x, (int)gridDim.x, kSacScratchSums, a.scratch)) {
     a.actor_loss[0] = sac_mean(s[0], a.rows);
     if (with_le) {
       a.ent_loss[0] = sac_neg_mean(s[1], a.rows);
@@ -193,41 +191,6 @@ __global__ __launch_bounds__(kBlock) void sac_scale_kernel(SacScaleArgs a) {
       if (a.o[k]) a.o[k][i] = a.up ? a.g[k][i] * up : 0.0f;
   }
   if (i == 0 && a.os) a.os[0] = a.up_s ? a.gs[0] * a.up_s[0] : 0.0f;
-}
-
-struct PolyakPair {
-  const float* src;
-  float* dst;
-  long long numel;
-};
-struct PolyakChunk {
-  int pair, chunk;
-};
-
-__global__ __launch_bounds__(kBlock) void polyak_kernel(const PolyakPair* __restrict__ pairs,
-                                                        const PolyakChunk* __restrict__ chunks, float tau_f, float om) {
-  const PolyakChunk c = chunks[blockIdx.x];
-  const PolyakPair pr = pairs[c.pair];
-  const long long off = (long long)c.chunk * kPolyakChunk;
-  const long long left = pr.numel - off;
-  const int count = left < kPolyakChunk ? (int)left : kPolyakChunk;
-  const float* const src = pr.src + off;
-  float* const dst = pr.dst + off;
-  int done = 0;
-  if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
-    const int n4 = count / 4;
-    for (int i = threadIdx.x; i < n4; i += kBlock) {
-      const float4 p = reinterpret_cast<const float4*>(src)[i];
-      float4 t = reinterpret_cast<float4*>(dst)[i];
-      t.x = polyak_value(t.x, p.x, tau_f, om);
-      t.y = polyak_value(t.y, p.y, tau_f, om);
-      t.z = polyak_value(t.z, p.z, tau_f, om);
-      t.w = polyak_value(t.w, p.w, tau_f, om);
-      reinterpret_cast<float4*>(dst)[i] = t;
-    }
-    done = 4 * n4;
-  }
-  for (int i = done + threadIdx.x; i < count; i += kBlock) dst[i] = polyak_value(dst[i], src[i], tau_f, om);
 }
 
 }  // namespace usv

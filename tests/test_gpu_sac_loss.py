@@ -2,8 +2,8 @@
 _loss_backward / usv_polyak_update).
 
 Bitwise, against the NumPy float32 restatement (tests/sac_loss_ref.py): every output of both losses, the scaled
-gradients for upstream 1, another scalar and None, Polyak (a pair of views 4 B off a 16-B boundary and a list with a
-zero-element tensor included), repeated calls and calls on a second stream.
+gradients for upstream 1, another scalar and None, Polyak (a pair of views 4 B off a 16-B boundary, a list with a
+zero-element tensor included, a list of 130 pairs), repeated calls and calls on a second stream.
 
 Against torch-CPU float64 autograd of SB3's lines: ten errors, each divided by the sum of the absolute magnitudes of
 its terms, measured over sac_loss_ref.ROWS, printed, and bounded at 4x the maximum measured on the MI355X (MEASURED
@@ -238,6 +238,44 @@ def test_polyak_equals_the_restatement_bitwise():
             pol.step(tau)
     with pytest.raises(UsvLibError):
         DevicePolyak([params[0]], [params[0]]).step(0.5)
+
+
+def test_polyak_over_130_pairs_equals_the_restatement_bitwise():
+    """130 pairs, 129 of them with elements (more than the 96 tensors a launch of a by-value table takes, should
+    Polyak ever move to one).  1 .. 9 elements each, packed into one buffer a float apart (so most are misaligned, and a
+    write past a tensor's end would show), a zero-element pair in the middle, and behind 99 others a pair of C + 1
+    elements (two chunks, a one-element tail) 4 B off a 16-B boundary.  The same list as two objects of 65 pairs each
+    gives the same bits."""
+    from gym_usv_amd import DevicePolyak
+    rng = np.random.default_rng(6)
+    sizes = [1 + i % 9 for i in range(128)]
+    sizes.insert(64, 0)
+    sizes.insert(100, S.C + 1)
+    spans, at = [], 0
+    for n in sizes:
+        if n > 9:
+            at += (1 - at) % 4                              # float 1 of a group of four: 4 B past the boundary
+        spans.append((at, at + n))
+        at += n + 1
+    p_flat, t_flat = to_dev(rng.standard_normal(at)), to_dev(rng.standard_normal(at))
+    assert p_flat.data_ptr() % 16 == 0 and t_flat.data_ptr() % 16 == 0
+    t_split = t_flat.clone()
+    views = lambda flat: [flat[a:b] for a, b in spans]      # noqa: E731
+    params, targets, halves = views(p_flat), views(t_flat), views(t_split)
+    assert len(params) == 130 and params[100].numel() == S.C + 1 and params[64].numel() == 0
+    assert params[100].data_ptr() % 16 == 4 and targets[100].data_ptr() % 16 == 4
+    whole = DevicePolyak(params, targets)
+    first, second = DevicePolyak(params[:65], halves[:65]), DevicePolyak(params[65:], halves[65:])
+    want, src = host(t_flat), host(p_flat)
+    for tau in (0.005, 0.3, 0.9):
+        whole.step(tau)
+        first.step(tau)
+        second.step(tau)
+        for a, b in spans:
+            want[a:b] = S.polyak(want[a:b], src[a:b], tau)
+        assert S.same(host(t_flat), want), tau              # the floats between the tensors included
+        assert S.same(host(t_split), want), tau
+    assert S.same(host(p_flat), src)
 
 
 def test_polyak_against_torch_on_the_device():

@@ -312,6 +312,18 @@ def test_entries_refuse_bad_arguments_without_gpu(lib):
     assert lib.usv_polyak_update(none, 1, None, 0, 1, 0.005, None) == 0      # nothing to do: no launch
 
 
+def test_polyak_of_empty_pairs_alone_needs_no_device(lib):
+    """A list whose every pair has numel == 0 is USV_OK before any HIP call: neither the pointers nor the table are
+    looked at."""
+    from gym_usv_amd import _lib
+    Pair = _lib.UsvPolyakPair
+    for n in (1, 3, 130):
+        arr = (Pair * n)(*(Pair(None if i % 2 else 8, None if i % 3 else 2, 0) for i in range(n)))
+        assert lib.usv_polyak_table_bytes(arr, n) == 0
+        for tau in (0.0, 0.005, 1.0):
+            assert lib.usv_polyak_update(arr, n, None, 0, 1, tau, None) == 0, (n, tau, lib.usv_last_error())
+
+
 def test_python_checks_need_no_device():
     import torch
     import gym_usv_amd
