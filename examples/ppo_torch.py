@@ -39,13 +39,24 @@ this image, so this is a compact PPO with the same hyper-parameters where they c
   ``DeviceSDE.evaluate``: the log-probability of the stored actions, the ratio and the clipped surrogate in one
   HIP launch and their gradients in two, in place of the torch ops of ``ActorCritic.dist``, ``log_prob``, ``exp``,
   ``clamp`` and ``min`` and their autograd.  Advantage normalisation, the value loss and ``-logp.mean()`` stay
-  torch.  ``--check-eval`` (a test mode) evaluates both heads on every minibatch and records
+  torch (``--loss-kernel`` below fuses them).  ``--check-eval`` (a test mode) evaluates both heads on every minibatch and records
   ``eval_logp_diff_max``, the largest ``|logp_kernel - logp_torch| / (1 + sum_k (d^2 / s2 + |ln s2|))`` of the
   update, read back once per update.
 * ``--adam-kernel`` (``train(..., adam_kernel=True)``): ``clip_grad_norm_``, ``Adam.step()`` and ``zero_grad`` of every
   minibatch are ``gym_usv_amd.DeviceAdam``: two HIP launches over the whole parameter list (the norm in a fixed
   summation order, then clip and Adam in one pass) in place of torch's ops per tensor, with torch's arithmetic up to
   rounding.  Nothing else changes.
+* ``--loss-kernel`` (``train(..., loss_kernel=True)``, in every mode): the minibatch loss is
+  ``gym_usv_amd.DevicePPOLoss.loss``: advantage normalisation, the ratio, clamp and min, the value loss, the entropy
+  term and the weighted sum in one C call (three launches with normalisation) and their gradients in one launch, in
+  place of some twenty torch ops each way.  With ``--eval-kernel`` the head is then called without the PPO
+  arguments and only gives the log-probability; with ``--no-sde`` the distribution's entropy goes in as a tensor.
+  The update's record gains ``approx_kl`` and ``clip_fraction`` (means over the update) and ``explained_variance``
+  (one call per update on the rollout's values and returns), read back with the other statistics once per update.
+  ``--check-loss`` (a test mode) also evaluates the torch lines on every minibatch and records ``loss_diff``, the
+  largest difference of each of the three losses over the sum of the magnitudes of its terms.
+* ``--clip-range-vf X`` (SB3's ``clip_range_vf``, default none) and ``--no-normalize-advantage`` (SB3's
+  ``normalize_advantage=False``) apply with and without ``--loss-kernel``.
 
 Rollout size at 4096 envs.  config_ppo's ``n_steps=2048, batch_size=64`` are for the reference's 4
 envs: 8 192 samples per update in 128 minibatches.  With 4096 envs the same n_steps would put 8.4 M
@@ -78,7 +89,7 @@ import torch.nn as nn  # noqa: E402
 
 CONFIG_PPO = {"n_stack": 5, "hidden": (256, 256), "log_std_init": -2.0, "use_sde": True, "sde_sample_freq": 4,
               "lr": 3e-4, "gamma": 0.99, "gae_lambda": 0.95, "clip": 0.2, "n_epochs": 10, "vf_coef": 0.5,
-              "ent_coef": 0.0, "max_grad_norm": 0.5}
+              "ent_coef": 0.0, "max_grad_norm": 0.5, "clip_range_vf": None, "normalize_advantage": True}
 SDE_EPS = 1e-6        # StateDependentNoiseDistribution.epsilon
 
 
@@ -126,7 +137,7 @@ class PPO:
     """Rollout + update over a ``UsvVectorEnv`` (any registered id with a Box action space)."""
 
     def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, frames=False, sde_kernel=False,
-                 eval_kernel=False, check_eval=False, adam_kernel=False, **cfg):
+                 eval_kernel=False, check_eval=False, adam_kernel=False, loss_kernel=False, check_loss=False, **cfg):
         from gym_usv_amd.sb3 import DeviceFrameStack
         self.cfg = dict(CONFIG_PPO, **cfg)
         self.env, self.n_steps, self.batch_size = env, n_steps, batch_size
@@ -143,6 +154,14 @@ class PPO:
             raise ValueError("eval_kernel=True and check_eval=True need fused=True and sde_kernel=True")
         self.eval_kernel, self.check_eval = eval_kernel, check_eval
         self._eval_diff = None                          # check_eval: the update's largest normalised |dlogp|
+        if check_loss and not loss_kernel:
+            raise ValueError("check_loss compares the loss kernel with torch: it needs loss_kernel=True")
+        self.loss_kernel, self.check_loss, self.losses_checked = loss_kernel, check_loss, 0
+        self.ppo_loss = self._ev = None
+        if loss_kernel:
+            from gym_usv_amd import DevicePPOLoss
+            self.ppo_loss = DevicePPOLoss(self.device)
+            self.loss_diff = torch.zeros(3, device=self.device)     # policy, value, entropy: the largest so far
         self.head = None
         if not fused:
             self.stack = DeviceFrameStack(self.N, D, self.cfg["n_stack"], self.device)
@@ -285,23 +304,30 @@ class PPO:
     def policy_terms(self, obs, actions, old_logp, a_):
         """(log_prob [B], policy loss, the torch distribution or None) of one minibatch.  ``eval_kernel``: the
         three come from ``DeviceSDE.evaluate`` on the policy's mean and detached latent; ``check_eval``: both heads
-        run and the largest normalised difference of their log-probabilities is kept on the device."""
+        run and the largest normalised difference of their log-probabilities is kept on the device.  ``a_`` None
+        (``loss_kernel``): the log-probability alone, no policy loss."""
         clip = self.cfg["clip"]
         if not (self.eval_kernel or self.check_eval):
             dist, _ = self.model.dist(obs)
             logp = dist.log_prob(actions).sum(-1)
+            if a_ is None:
+                return logp, None, dist
             ratio = (logp - old_logp).exp()
             return logp, -torch.min(ratio * a_, ratio.clamp(1 - clip, 1 + clip) * a_).mean(), dist
         lat = self.model.pi_body(obs)
         mean, std = self.model.mu(lat), self.model.log_std.exp()
         lat = lat.detach()
-        if self.eval_kernel:
+        if self.eval_kernel and a_ is None:
+            logp, pg = self.head.evaluate(mean, lat, std, actions).log_prob, None
+        elif self.eval_kernel:
             ev = self.head.evaluate(mean, lat, std, actions, old_logp, a_, clip)
             logp, pg = ev.log_prob, -ev.surrogate.mean()
         if self.check_eval or not self.eval_kernel:
             s2 = (lat * lat) @ (std ** 2) + SDE_EPS
             t_logp = torch.distributions.Normal(mean, torch.sqrt(s2), validate_args=False).log_prob(actions).sum(-1)
-        if not self.eval_kernel:
+        if not self.eval_kernel and a_ is None:
+            logp, pg = t_logp, None
+        elif not self.eval_kernel:
             ratio = (t_logp - old_logp).exp()
             logp, pg = t_logp, -torch.min(ratio * a_, ratio.clamp(1 - clip, 1 + clip) * a_).mean()
         if self.check_eval:
@@ -314,9 +340,17 @@ class PPO:
         return logp, pg, None
 
     def update_record(self, stats):
-        s = torch.stack(stats).mean(0).tolist()
+        s = torch.stack(stats).mean(0)
+        if self.loss_kernel:                            # one read for the update's means and explained_variance
+            s = torch.cat((s, self._ev.reshape(1)))
+        s = s.tolist()
         rec = {"policy_loss": s[0], "value_loss": s[1], "entropy": s[2],
                "std_mean": float(self.model.log_std.detach().exp().mean())}
+        if self.loss_kernel:
+            rec["approx_kl"], rec["clip_fraction"], rec["explained_variance"] = s[3], s[4], s[5]
+        if self.check_loss:                             # the largest so far
+            rec["loss_diff"] = dict(zip(("policy", "value", "entropy"), self.loss_diff.tolist()))
+            rec["losses_checked"] = self.losses_checked
         if self.check_eval:
             rec["eval_logp_diff_max"], self._eval_diff = float(self._eval_diff), None
         return rec
@@ -328,28 +362,81 @@ class PPO:
             nn.utils.clip_grad_norm_(self.model.parameters(), self.cfg["max_grad_norm"])
         self.opt.step()
 
+    def minibatch_loss(self, obs, act, old_logp, adv, ret, old_val):
+        """(loss, the minibatch's statistics) of SB3's ``PPO.train`` lines: (policy loss, value loss, entropy) and,
+        with ``loss_kernel``, approx_kl and clip_fraction behind them."""
+        c = self.cfg
+        if self.loss_kernel:
+            return self.kernel_loss(obs, act, old_logp, adv, ret, old_val)
+        a_ = adv
+        if c["normalize_advantage"] and len(a_) > 1:
+            a_ = (a_ - a_.mean()) / (a_.std() + 1e-8)
+        logp, pg, dist = self.policy_terms(obs, act, old_logp, a_)
+        if c["clip_range_vf"] is None:
+            vl = ((self.model.value(obs) - ret) ** 2).mean()
+        else:
+            vp = old_val + (self.model.value(obs) - old_val).clamp(-c["clip_range_vf"], c["clip_range_vf"])
+            vl = ((vp - ret) ** 2).mean()
+        ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
+        loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
+        return loss, torch.stack((pg.detach(), vl.detach(), ent.detach()))
+
+    def kernel_loss(self, obs, act, old_logp, adv, ret, old_val):
+        """``minibatch_loss`` through ``DevicePPOLoss.loss``: the head gives the log-probability alone."""
+        c = self.cfg
+        logp, _, dist = self.policy_terms(obs, act, old_logp, None)
+        values = self.model.value(obs)
+        entropy = None if c["use_sde"] else dist.entropy().sum(-1)
+        cvf = c["clip_range_vf"]
+        out = self.ppo_loss.loss(logp, old_logp, adv, values, ret, clip_range=c["clip"], vf_coef=c["vf_coef"],
+                                 ent_coef=c["ent_coef"], normalize_advantage=c["normalize_advantage"],
+                                 old_values=None if cvf is None else old_val, clip_range_vf=cvf, entropy=entropy)
+        if self.check_loss:
+            self.compare_loss(out, logp, values, entropy, old_logp, adv, ret, old_val)
+        return out.loss, torch.stack((out.policy_loss, out.value_loss, -out.entropy_loss, out.approx_kl,
+                                      out.clip_fraction))
+
+    @torch.no_grad()
+    def compare_loss(self, out, logp, values, entropy, old_logp, adv, ret, old_val):
+        """``check_loss``: the torch lines on the same tensors; each loss's difference over the sum of the magnitudes
+        of its terms (a normalised advantage's terms are |adv| and |mean| over the std)."""
+        c = self.cfg
+        clip, cvf = c["clip"], c["clip_range_vf"]
+        a_, mag = adv, adv.abs()
+        if c["normalize_advantage"] and len(a_) > 1:
+            mean, std = a_.mean(), a_.std()
+            a_, mag = (a_ - mean) / (std + 1e-8), (mag + mean.abs()) / (std + 1e-8)
+        ratio = (logp - old_logp).exp()
+        pg = -torch.min(ratio * a_, ratio.clamp(1 - clip, 1 + clip) * a_).mean()
+        vp = values if cvf is None else old_val + (values - old_val).clamp(-cvf, cvf)
+        vl = ((vp - ret) ** 2).mean()
+        term = -logp if entropy is None else entropy
+        ours = torch.stack((out.policy_loss, out.value_loss, -out.entropy_loss))
+        diff = (ours - torch.stack((pg, vl, term.mean()))).abs()
+        scale = torch.stack(((ratio * mag).mean(), ((vp.abs() + ret.abs()) ** 2).mean(), term.abs().mean()))
+        r = torch.where(scale > 0, diff / scale, diff * float("inf")).nan_to_num(nan=0.0)   # a zero scale wants a zero diff
+        self.loss_diff = torch.maximum(self.loss_diff, r)
+        self.losses_checked += 1
+
     def update(self):
         c = self.cfg
         adv, ret = self.advantages()
         M = self.n_steps * self.N
+        if self.loss_kernel:
+            self._ev = self.ppo_loss.explained_variance(self.b_val, ret)
         if self.frames:
             return self.update_frames(M)
         obs = self.b_obs.reshape(M, -1)
         act = self.b_act.reshape(M, -1)
-        logp0, adv, ret = self.b_logp.reshape(M), adv.reshape(M), ret.reshape(M)
+        logp0, val0, adv, ret = self.b_logp.reshape(M), self.b_val.reshape(M), adv.reshape(M), ret.reshape(M)
         stats = []
         for _ in range(c["n_epochs"]):
             perm = torch.randperm(M, device=self.device)
             for k in range(0, M, self.batch_size):
                 i = perm[k:k + self.batch_size]
-                a_ = adv[i]
-                a_ = (a_ - a_.mean()) / (a_.std() + 1e-8)
-                logp, pg, dist = self.policy_terms(obs[i], act[i], logp0[i], a_)
-                vl = ((self.model.value(obs[i]) - ret[i]) ** 2).mean()
-                ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
-                loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
+                loss, stat = self.minibatch_loss(obs[i], act[i], logp0[i], adv[i], ret[i], val0[i])
                 self.gradient_step(loss)
-                stats.append(torch.stack((pg.detach(), vl.detach(), ent.detach())))
+                stats.append(stat)
         return self.update_record(stats)
 
     def update_frames(self, M):
@@ -361,14 +448,10 @@ class PPO:
             perm = torch.randperm(M, device=self.device)
             for k in range(0, M, self.batch_size):
                 mb = self.ro.gather(perm[k:k + self.batch_size])
-                a_ = mb.advantages
-                a_ = (a_ - a_.mean()) / (a_.std() + 1e-8)
-                logp, pg, dist = self.policy_terms(mb.observations, mb.actions, mb.old_log_prob, a_)
-                vl = ((self.model.value(mb.observations) - mb.returns) ** 2).mean()
-                ent = -logp.mean() if c["use_sde"] else dist.entropy().sum(-1).mean()
-                loss = pg + c["vf_coef"] * vl - c["ent_coef"] * ent
+                loss, stat = self.minibatch_loss(mb.observations, mb.actions, mb.old_log_prob, mb.advantages, mb.returns,
+                                                 mb.old_values)
                 self.gradient_step(loss)
-                stats.append(torch.stack((pg.detach(), vl.detach(), ent.detach())))
+                stats.append(stat)
         return self.update_record(stats)
 
     def episode_stats(self):
@@ -391,11 +474,15 @@ class PPO:
 
 
 def train(env_id="usv-simple", envs=4096, updates=10, n_steps=32, batch_size=4096, seed=0, log=print, fused=False,
-          frames=False, sde_kernel=False, eval_kernel=False, check_eval=False, adam_kernel=False, **cfg):
+          frames=False, sde_kernel=False, eval_kernel=False, check_eval=False, adam_kernel=False, loss_kernel=False,
+          check_loss=False, **cfg):
     import gym_usv_amd
+    if check_loss and not loss_kernel:
+        raise ValueError("check_loss compares the loss kernel with torch: it needs loss_kernel=True")
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False)   # each step is consumed at once
     ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, frames=frames,
-              sde_kernel=sde_kernel, eval_kernel=eval_kernel, check_eval=check_eval, adam_kernel=adam_kernel, **cfg)
+              sde_kernel=sde_kernel, eval_kernel=eval_kernel, check_eval=check_eval, adam_kernel=adam_kernel,
+              loss_kernel=loss_kernel, check_loss=check_loss, **cfg)
     hist = []
     t0 = time.perf_counter()
     for u in range(updates):
@@ -429,6 +516,12 @@ def main():
                     help="with --sde-kernel: evaluate both heads on every minibatch and record eval_logp_diff_max")
     ap.add_argument("--adam-kernel", action="store_true",
                     help="clip_grad_norm_ and Adam.step() of every minibatch through DeviceAdam")
+    ap.add_argument("--loss-kernel", action="store_true",
+                    help="the minibatch loss, approx_kl and clip_fraction through DevicePPOLoss; explained_variance per update")
+    ap.add_argument("--check-loss", action="store_true",
+                    help="with --loss-kernel: also evaluate the torch lines on every minibatch and record loss_diff")
+    ap.add_argument("--clip-range-vf", type=float, default=None, help="SB3's clip_range_vf (default: none)")
+    ap.add_argument("--no-normalize-advantage", action="store_true", help="SB3's normalize_advantage=False")
     ap.add_argument("--log", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
     if a.frames and not a.fused:
@@ -437,6 +530,8 @@ def main():
         ap.error("--sde-kernel needs --fused and gSDE (no --no-sde)")
     if (a.eval_kernel or a.check_eval) and not a.sde_kernel:
         ap.error("--eval-kernel and --check-eval need --sde-kernel")
+    if a.check_loss and not a.loss_kernel:
+        ap.error("--check-loss needs --loss-kernel")
     f = open(a.log, "a") if a.log else None
 
     def log(s):
@@ -449,10 +544,13 @@ def main():
                                    "n_steps": a.n_steps, "batch_size": a.batch_size, "seed": a.seed,
                                    "fused": a.fused, "frames": a.frames, "sde_kernel": a.sde_kernel,
                                    "eval_kernel": a.eval_kernel, "check_eval": a.check_eval,
-                                   "adam_kernel": a.adam_kernel}}))
+                                   "adam_kernel": a.adam_kernel, "loss_kernel": a.loss_kernel,
+                                   "check_loss": a.check_loss, "clip_range_vf": a.clip_range_vf,
+                                   "normalize_advantage": not a.no_normalize_advantage}}))
     train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, fused=a.fused, frames=a.frames,
           sde_kernel=a.sde_kernel, eval_kernel=a.eval_kernel, check_eval=a.check_eval, adam_kernel=a.adam_kernel,
-          use_sde=not a.no_sde)
+          loss_kernel=a.loss_kernel, check_loss=a.check_loss, use_sde=not a.no_sde, clip_range_vf=a.clip_range_vf,
+          normalize_advantage=not a.no_normalize_advantage)
 
 
 if __name__ == "__main__":

@@ -39,6 +39,10 @@
 //   usv_optim_math.hpp    optimizer step: Adam's scalars and element update, the clip, the norm's order (host C++, no HIP)
 //   usv_optim.hpp         kernels over a tensor list: clip_grad_norm_ and Adam (the list passed by value), Polyak (a
 //                         device table), one element loop under both (usv_adam_step / usv_polyak_update)
+//   usv_ppo_math.hpp      PPO loss: moments, the row's terms and unit gradients, the finish, explained variance
+//                         (host C++, no HIP)
+//   usv_ppo.hpp           PPO loss: two moment kernels and the fused loss on usv_sac.hpp's reduction
+//                         (usv_ppo_loss / usv_ppo_explained_variance)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -70,7 +74,8 @@
 #include "usv_replay.hpp"
 #include "usv_sac.hpp"           // (after the others: every kernel before it keeps its place in the code object)
 #include "usv_caps.hpp"          // (after usv_sac.hpp, for the same reason)
-#include "usv_optim.hpp"         // (last, for the same reason)
+#include "usv_optim.hpp"         // (after usv_caps.hpp, for the same reason)
+#include "usv_ppo.hpp"           // (last, for the same reason)
 
 // ============================================================================= host side
 using namespace usv;
@@ -1846,6 +1851,57 @@ int usv_adam_step(const usv_adam_tensor* tensors, int32_t n, float* m, float* v,
     const OptimAdamArgs a{tab, m, v, clip ? norm_out : nullptr, (float)max_grad_norm, sc};
     hipLaunchKernelGGL(optim_adam_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
   });
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- fused PPO loss (usv_ppo.hpp)
+static int ppo_bufs(const Buf* b, size_t nb, int& dev) { return refuse_bufs(b, nb, dev, "usv_ppo", "scratch"); }
+
+size_t usv_ppo_scratch_floats(int32_t rows) { return rows >= 1 ? ppo_scratch_floats(rows) : 0; }
+
+int usv_ppo_loss(int32_t rows, const float* logp, const float* old_logp, const float* adv, const float* values,
+                 const float* old_values, const float* returns, const float* entropy, int32_t normalize, float clip,
+                 float clip_vf, float ent_coef, float vf_coef, float* moments, float* out, float* g_logp,
+                 float* g_values, float* g_entropy, float* scratch, void* stream) {
+  int dev;
+  if (rows < 1) return fail(USV_ERR_ARG, "usv_ppo_loss: rows must be >= 1");
+  if (!ppo_range_ok(clip)) return fail(USV_ERR_ARG, "usv_ppo_loss: clip must be finite and >= 0");
+  if (old_values ? !ppo_range_ok(clip_vf) : clip_vf != 0.0f)
+    return fail(USV_ERR_ARG, old_values ? "usv_ppo_loss: clip_vf must be finite and >= 0"
+                                        : "usv_ppo_loss: old_values and clip_vf come together (clip_vf is 0 without old_values)");
+  if (g_entropy && !entropy) return fail(USV_ERR_ARG, "usv_ppo_loss: g_entropy needs entropy");
+  const Buf all[] = {{scratch, 16},  {logp, 4},          {old_logp, 4},      {adv, 4},          {values, 4},
+                     {returns, 4},   {moments, 4},       {out, 4},           {old_values, 4, true}, {entropy, 4, true},
+                     {g_logp, 4, true}, {g_values, 4, true}, {g_entropy, 4, true}};
+  if (int rc = ppo_bufs(all, 13, dev)) return rc;
+  DeviceGuard g(dev);
+  const dim3 grid((unsigned)sac_partials(rows)), block(kBlock);
+  const bool norm = normalize != 0 && rows > 1;
+  if (norm) {
+    const PpoMomentArgs m{rows, adv, nullptr, moments, nullptr, scratch};
+    hipLaunchKernelGGL(ppo_sum_kernel, grid, block, 0, (hipStream_t)stream, m);
+    hipLaunchKernelGGL(ppo_sqdev_kernel, grid, block, 0, (hipStream_t)stream, m);
+  }
+  const PpoLossArgs a{rows, PpoForm{norm, old_values != nullptr, entropy != nullptr, clip, clip_vf, ent_coef, vf_coef},
+                      logp, old_logp, adv, values, old_values, returns, entropy, moments,
+                      out, g_logp, g_values, g_entropy, scratch};
+  hipLaunchKernelGGL(ppo_loss_kernel, grid, block, 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_ppo_explained_variance(int32_t rows, const float* values, const float* returns, float* out, float* scratch,
+                               void* stream) {
+  int dev;
+  if (rows < 1) return fail(USV_ERR_ARG, "usv_ppo_explained_variance: rows must be >= 1");
+  const Buf all[] = {{scratch, 16}, {values, 4}, {returns, 4}, {out, 4}};
+  if (int rc = ppo_bufs(all, 4, dev)) return rc;
+  DeviceGuard g(dev);
+  const dim3 grid((unsigned)sac_partials(rows)), block(kBlock);
+  const PpoMomentArgs m{rows, returns, values, scratch + kPpoScratchMeans, out, scratch};
+  hipLaunchKernelGGL(ppo_sum_kernel, grid, block, 0, (hipStream_t)stream, m);
+  hipLaunchKernelGGL(ppo_sqdev_kernel, grid, block, 0, (hipStream_t)stream, m);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

@@ -3,8 +3,8 @@
 // entropy-coefficient losses with their gradients at unit upstream.  The arithmetic and the summation order are
 // usv_sac_math.hpp's.  (polyak_update over a list of tensors is usv_optim.hpp's, next to the element loop it shares.)
 //
-// The reduction that these kernels, caps_loss_kernel (usv_caps.hpp) and optim_sqsum_kernel (usv_optim.hpp) share has
-// two forms and no other: sac_for_rows, a thread's rows of its partial, and sac_finish, from the strands' sums to the
+// The reduction that these kernels, caps_loss_kernel (usv_caps.hpp), optim_sqsum_kernel (usv_optim.hpp) and the
+// ppo kernels (usv_ppo.hpp, five floats per partial) share has two forms and no other: sac_for_rows, a thread's rows of its partial, and sac_finish, from the strands' sums to the
 // one thread that holds the totals.
 //
 //   sac_critic_kernel, sac_policy_kernel

@@ -212,6 +212,10 @@ SIGNATURES = [
     ("usv_adam_step", ctypes.c_int, [ctypes.POINTER(UsvAdamTensor), _i32, _vp, _vp, _sz, _i64, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _sz, _vp,
                                      _vp]),
+    ("usv_ppo_scratch_floats", _sz, [_i32]),
+    ("usv_ppo_loss", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp]),
+    ("usv_ppo_explained_variance", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _LIBS = {}

@@ -853,6 +853,42 @@ int usv_adam_step(const usv_adam_tensor* tensors_host, int32_t n, float* m, floa
                   double lr, double beta1, double beta2, double eps, double max_grad_norm /* < 0: none */,
                   float* scratch, size_t scratch_floats, float* norm_out, void* stream);
 
+/* ---- Fused PPO loss: the loss lines of SB3's PPO.train (ppo/ppo.py) for one minibatch, with approx_kl, clip_fraction
+ * and common/utils.py's explained_variance (ABI v5 additions).  Handle-free and stream-ordered like the usv_sac_*
+ * entries, with their rules for buffers (f32 on one device, 4-B aligned) and for what is refused.  The arithmetic
+ * and the fixed summation order are gym-usv_amd/csrc/usv_ppo_math.hpp's; tests/ppo_loss_ref.py restates them.
+ *
+ * usv_ppo_loss, rows [rows] each; one call issues up to three launches:
+ *   with normalize != 0 and rows > 1:  moments[0] = mean(adv);  moments[1] = std(adv), unbiased, two passes;
+ *     a = (adv - mean) / (std + 1e-8);  otherwise a = adv and moments is not written
+ *   ratio = exp(logp - old_logp);  policy_loss = -mean(min(ratio a, clamp(ratio, 1 - clip, 1 + clip) a))
+ *   vp = values, or old_values + clamp(values - old_values, -clip_vf, clip_vf) where old_values is given
+ *   value_loss = mean((returns - vp)^2);  entropy_loss = -mean(entropy), or -mean(-logp) where entropy is NULL
+ *   out[0] = loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss
+ *   out[1..5] = policy_loss, value_loss, entropy_loss, approx_kl = mean((ratio - 1) - (logp - old_logp)),
+ *               clip_fraction = mean(|ratio - 1| > clip)
+ *   g_logp, g_values, g_entropy [rows]: the gradients of loss at unit upstream (each optional: NULL under no_grad;
+ *   g_entropy needs entropy); torch.min's and torch.clamp's ties as autograd has them.  The backward is
+ *   usv_sac_loss_backward on the three arrays.
+ * adv, old_logp, old_values and returns are data.  Without old_values, clip_vf is 0.
+ *
+ * usv_ppo_explained_variance: out[0] = 1 - var(returns - values) / var(returns), population variances in the same
+ * two-pass form, NaN where var(returns) == 0; two launches.
+ *
+ * scratch: usv_ppo_scratch_floats(rows) floats (0 for rows < 1), 16-B aligned, zeroed once when it is allocated; a
+ * call leaves its first word zero again.  Calls that share a scratch must be stream-ordered.  Nothing depends on the
+ * grid, the stream or the order in which blocks end: every output is bitwise reproducible.
+ * Refused: rows < 1, a clip or clip_vf that is NaN, infinite or negative, a clip_vf other than 0 without old_values,
+ * g_entropy without entropy, and what the usv_sac_* entries refuse of buffers. */
+size_t usv_ppo_scratch_floats(int32_t rows);
+int usv_ppo_loss(int32_t rows, const float* logp, const float* old_logp, const float* adv, const float* values,
+                 const float* old_values /* NULL: no clip_range_vf */, const float* returns,
+                 const float* entropy /* NULL: -logp */, int32_t normalize, float clip, float clip_vf, float ent_coef,
+                 float vf_coef, float* moments /* 2 floats */, float* out /* loss + 5 statistics */, float* g_logp,
+                 float* g_values, float* g_entropy /* each [rows] or NULL */, float* scratch, void* stream);
+int usv_ppo_explained_variance(int32_t rows, const float* values, const float* returns, float* out /* 1 float */,
+                               float* scratch, void* stream);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
