@@ -54,6 +54,16 @@ is a compact SAC with config_sac's hyper-parameters where they carry over:
   ``gym_usv_amd.DeviceAdam``, one HIP launch per ``step()`` over the whole parameter list in place of torch's Adam ops,
   with torch's arithmetic up to rounding.  Nothing else changes.
 
+* ``graph=True`` (``--graph``; needs ``device_replay``, ``sde_kernel``, ``loss_kernel`` and ``adam_kernel``, with ``caps`` also
+  ``caps_kernel``, and neither ``check_loss`` nor ``check_caps``; anything else is a ``ValueError`` at start): a gradient
+  step is recorded once as a HIP graph (``gym_usv_amd.capture_step``) and replayed.  Per gradient step the ``randint`` and
+  the one replay gather launch stay eager, the gather writing straight into static minibatch tensors; one ``replay()``
+  covers the rest: both ``reset_noise()`` calls, the critic step, the actor and entropy-coefficient step with CAPS, three
+  ``DeviceAdam.step()`` calls and ``DevicePolyak.step()``.  The trainer objects are then made with ``capturable=True`` (their
+  step and noise counters live in device memory).  The warm-up and capture calls run on the first minibatch and are
+  undone (parameters, optimizer state and noise epochs are put back), so the run takes the gradient steps of the run
+  without ``graph``; the logged losses are read from the graph's static outputs after each replay.
+
 ``learning_starts`` counts vector steps here (SB3 counts transitions: 50 000 of them are 12 steps of 4096 envs).  The loop
 collects ``train_freq`` steps, then takes ``gradient_steps`` gradient steps, as SB3's ``learn`` does.
 Whole runs of the two buffer modes are two samples of one algorithm: torch's own kernels need not be
@@ -63,6 +73,8 @@ bitwise reproducible.
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel --loss-kernel
     python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel --loss-kernel --caps --caps-kernel
+    python examples/sac_torch.py --envs 4096 --steps 400 --device-replay --sde-kernel --loss-kernel --caps --caps-kernel \
+        --adam-kernel --graph
 """
 from __future__ import annotations
 
@@ -206,7 +218,7 @@ class TorchReplay:
 
 class SAC:
     def __init__(self, env, seed=0, device_replay=True, check_replay=False, sde_kernel=False, loss_kernel=False,
-                 check_loss=False, caps=False, caps_kernel=False, check_caps=False, adam_kernel=False, **cfg):
+                 check_loss=False, caps=False, caps_kernel=False, check_caps=False, adam_kernel=False, graph=False, **cfg):
         from gym_usv_amd import DeviceAdam, DeviceCAPS, DevicePolyak, DeviceReplay, DeviceSACLoss, DeviceSDE
         from gym_usv_amd.replay import discount_table
         from gym_usv_amd.wrappers import DeviceWrappers
@@ -221,17 +233,21 @@ class SAC:
         self.target.load_state_dict(self.critic.state_dict())
         self.log_ent = torch.zeros(1, device=d, requires_grad=True)      # ent_coef 'auto': initial value 1
         self.target_entropy = -float(A)
+        check_graph_args(graph, device_replay, sde_kernel, loss_kernel, adam_kernel, caps, caps_kernel, check_loss,
+                         check_caps)
+        self.graph, self.captured, self.static_mb = graph, None, None
+        cap = {"capturable": True} if graph else {}         # counters in device memory: a replayed step counts
         adam = DeviceAdam if adam_kernel else torch.optim.Adam      # the same calls either way: zero_grad, step
-        self.opt_a = adam(self.actor.parameters(), lr=c["lr"])
-        self.opt_c = adam(self.critic.parameters(), lr=c["lr"])
-        self.opt_e = adam([self.log_ent], lr=c["lr"])
+        self.opt_a = adam(self.actor.parameters(), lr=c["lr"], **cap)
+        self.opt_c = adam(self.critic.parameters(), lr=c["lr"], **cap)
+        self.opt_e = adam([self.log_ent], lr=c["lr"], **cap)
         lo, hi = env.single_action_space.low, env.single_action_space.high
         self.a_lo = torch.as_tensor(lo, device=d, dtype=torch.float32)
         self.a_hi = torch.as_tensor(hi, device=d, dtype=torch.float32)
         self.head_env = self.head_mb = None
         if sde_kernel:      # rows = global env ids / positions in the minibatch; seeds other than the env's
             self.head_env = DeviceSDE(self.N, c["net_arch"][-1], A, d, seed + 1, lo, hi)
-            self.head_mb = DeviceSDE(c["batch_size"], c["net_arch"][-1], A, d, seed + 2, lo, hi)
+            self.head_mb = DeviceSDE(c["batch_size"], c["net_arch"][-1], A, d, seed + 2, lo, hi, **cap)
         self.sde_steps = 0
         if check_loss and not loss_kernel:
             raise ValueError("check_loss compares the loss kernels with torch: it needs loss_kernel=True")
@@ -244,7 +260,7 @@ class SAC:
         check_caps_args(caps, caps_kernel, check_caps, c["n_steps"])
         self.caps, self.caps_dev, self.check_caps, self.caps_checked = caps, None, check_caps, 0
         if caps_kernel:                                     # rows = positions in the minibatch; its own seed
-            self.caps_dev = DeviceCAPS(d, seed + 3, c["lambda_t"], c["lambda_s"], c["eps_s"], squash=True)
+            self.caps_dev = DeviceCAPS(d, seed + 3, c["lambda_t"], c["lambda_s"], c["eps_s"], squash=True, **cap)
         self.caps_diff = torch.zeros((), device=d)
         self.wr = DeviceWrappers(self.N, D, k, d, env.reward.dtype)
         self.rb = self.shadow = None
@@ -291,7 +307,7 @@ class SAC:
         c = self.cfg
         size = self.rb.size if self.rb is not None else self.shadow.size
         idx = torch.randint(0, size * self.N, (c["batch_size"],), device=self.device)
-        legs = (lambda: self.rb.gather_nstep(idx), lambda: self.shadow.gather_nstep(idx, c["n_steps"], self.table))
+        legs = (lambda: self.rb.gather_nstep(idx, out=self.static_mb), lambda: self.shadow.gather_nstep(idx, c["n_steps"], self.table))
         mb = legs[0 if self.device_replay else 1]()
         if self.rb is not None and self.shadow is not None:
             other = legs[1 if self.device_replay else 0]()
@@ -405,21 +421,54 @@ class SAC:
         self._worst(2, (pl.ent_coef_loss - ent_loss).abs(),
                     self.log_ent.abs().squeeze() * (logp.abs() + abs(self.target_entropy)).mean())
 
+    def gradient_step(self, mb):
+        """One gradient step on ``mb`` behind the minibatch; with the loss kernels its statistics, one tensor (what
+        ``graph=True`` records and replays), otherwise what the torch lines of ``train`` go on from."""
+        if self.head_mb is not None:
+            self.head_mb.reset_noise()                      # SAC.train: one matrix per gradient step
+        a_pi, logp, mean = self.policy(mb.observations)
+        ent = self.log_ent.detach().exp()
+        smooth, extra = None, ()
+        if self.caps:
+            smooth, *extra = self.smooth(mb, mean)
+        if self.loss is None:
+            return a_pi, logp, ent, smooth, extra
+        actor_loss, critic_loss, ent_loss = self.kernel_step(mb, a_pi, logp, ent, smooth)
+        return torch.stack((actor_loss, critic_loss, ent.squeeze(), ent_loss, *extra))
+
+    def capture(self, mb):
+        """Records ``gradient_step`` on the static minibatch ``mb``.  The warm-up and capture calls train on it: what
+        they changed is put back, so the first replay is the run's first gradient step."""
+        from gym_usv_amd import capture_step
+        opts = (self.opt_a, self.opt_c, self.opt_e)
+        nets = [p for m in (self.actor, self.critic, self.target) for p in m.parameters()] + [self.log_ent]
+        kept = [p.detach().clone() for p in nets]
+        states = [o.state_dict() for o in opts]
+        epochs = [x.epoch for x in (self.head_mb, self.caps_dev) if x is not None]
+        self.static_mb = mb
+        self.captured = capture_step(lambda: self.gradient_step(mb))
+        with torch.no_grad():
+            for p, k in zip(nets, kept):
+                p.copy_(k)                                  # in place: the graph holds the addresses
+        for o, sd in zip(opts, states):
+            o.load_state_dict(sd)
+        for x, e in zip([x for x in (self.head_mb, self.caps_dev) if x is not None], epochs):
+            x.epoch = e
+
     def train(self, gradient_steps):
         c, stats = self.cfg, []
         for _ in range(gradient_steps):
             mb = self.minibatch()
-            if self.head_mb is not None:
-                self.head_mb.reset_noise()                  # SAC.train: one matrix per gradient step
-            a_pi, logp, mean = self.policy(mb.observations)
-            ent = self.log_ent.detach().exp()
-            smooth, extra = None, ()
-            if self.caps:
-                smooth, *extra = self.smooth(mb, mean)
-            if self.loss is not None:
-                actor_loss, critic_loss, ent_loss = self.kernel_step(mb, a_pi, logp, ent, smooth)
-                stats.append(torch.stack((actor_loss, critic_loss, ent.squeeze(), ent_loss, *extra)))
+            if self.graph:
+                if self.captured is None:
+                    self.capture(mb)                        # from here on minibatch() gathers into mb's tensors
+                stats.append(self.captured.replay().clone())    # the static output, before the next replay rewrites it
                 continue
+            out = self.gradient_step(mb)
+            if self.loss is not None:
+                stats.append(out)
+                continue
+            a_pi, logp, ent, smooth, extra = out
             ent_loss = -(self.log_ent * (logp.detach() + self.target_entropy)).mean()
             self.opt_e.zero_grad(set_to_none=True)
             ent_loss.backward()
@@ -476,20 +525,36 @@ def check_caps_args(caps, caps_kernel, check_caps, n_steps):
                          "sample does not carry")
 
 
+def check_graph_args(graph, device_replay, sde_kernel, loss_kernel, adam_kernel, caps, caps_kernel, check_loss, check_caps):
+    if not graph:
+        return
+    missing = [name for name, on in (("--device-replay", device_replay), ("--sde-kernel", sde_kernel),
+                                     ("--loss-kernel", loss_kernel), ("--adam-kernel", adam_kernel),
+                                     ("--caps-kernel", caps_kernel or not caps)) if not on]
+    if missing:
+        raise ValueError("--graph records the gradient step of the HIP kernels: it also needs " + " ".join(missing) +
+                         " (a step with torch's own noise, losses or optimizers is not recorded)")
+    if check_loss or check_caps:
+        raise ValueError("--graph does not go with --check-loss or --check-caps: the test modes run outside a graph")
+
+
 def train(env_id="usv-simple", envs=4096, steps=400, seed=0, log=print, device_replay=True, check_replay=False,
           max_episode_steps=None, sde_kernel=False, loss_kernel=False, check_loss=False, caps=False, caps_kernel=False,
-          check_caps=False, adam_kernel=False, **cfg):
+          check_caps=False, adam_kernel=False, graph=False, keep=None, **cfg):
     """``steps`` vector steps of ``envs`` envs.  Returns one record per training round (``train_freq``
     steps, then ``gradient_steps`` gradient steps once ``learning_starts`` steps are in the buffer)."""
     import gym_usv_amd
     if check_loss and not loss_kernel:
         raise ValueError("check_loss compares the loss kernels with torch: it needs loss_kernel=True")
     check_caps_args(caps, caps_kernel, check_caps, dict(CONFIG_SAC, **cfg)["n_steps"])
+    check_graph_args(graph, device_replay, sde_kernel, loss_kernel, adam_kernel, caps, caps_kernel, check_loss, check_caps)
     kw = {} if max_episode_steps is None else {"max_episode_steps": max_episode_steps}
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False, **kw)
     sac = SAC(env, seed=seed, device_replay=device_replay, check_replay=check_replay, sde_kernel=sde_kernel,
               loss_kernel=loss_kernel, check_loss=check_loss, caps=caps, caps_kernel=caps_kernel, check_caps=check_caps,
-              adam_kernel=adam_kernel, **cfg)
+              adam_kernel=adam_kernel, graph=graph, **cfg)
+    if keep is not None:                                    # the caller's list: the trainer, for what it wants to read
+        keep.append(sac)
     c, hist, done_steps = sac.cfg, [], 0
     t0 = time.perf_counter()
     while done_steps < steps:
@@ -528,13 +593,15 @@ def main():
     ap.add_argument("--caps-kernel", action="store_true", help="with --caps: through DeviceCAPS instead of torch lines")
     ap.add_argument("--check-caps", action="store_true", help="with --caps-kernel: also run the torch lines and compare")
     ap.add_argument("--adam-kernel", action="store_true", help="the three Adam optimizers through DeviceAdam")
+    ap.add_argument("--graph", action="store_true",
+                    help="record a gradient step as a HIP graph and replay it (needs the four kernel flags above)")
     ap.add_argument("--lambda-t", type=float, default=CONFIG_SAC["lambda_t"])
     ap.add_argument("--lambda-s", type=float, default=CONFIG_SAC["lambda_s"])
     ap.add_argument("--eps-s", type=float, default=CONFIG_SAC["eps_s"])
     a = ap.parse_args()
     train(a.env_id, a.envs, a.steps, a.seed, device_replay=a.device_replay, check_replay=a.check_replay,
           sde_kernel=a.sde_kernel, loss_kernel=a.loss_kernel, check_loss=a.check_loss, caps=a.caps, caps_kernel=a.caps_kernel,
-          check_caps=a.check_caps, adam_kernel=a.adam_kernel, buffer_size=a.buffer_size, batch_size=a.batch_size,
+          check_caps=a.check_caps, adam_kernel=a.adam_kernel, graph=a.graph, buffer_size=a.buffer_size, batch_size=a.batch_size,
           n_steps=a.n_steps, lambda_t=a.lambda_t, lambda_s=a.lambda_s, eps_s=a.eps_s)
 
 

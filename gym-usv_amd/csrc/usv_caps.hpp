@@ -7,6 +7,8 @@
 //       whose four elements are all there and 16-B aligned in both arrays moves them with one 16-B load and one 16-B
 //       store; any other takes them one by one (rows of 715 floats: every fourth row is aligned).  Each thread reads
 //       its elements before it writes them, so out may be obs.
+//   caps_perturb_dev_kernel
+//       The same text (usv_caps_noise.inc) with the epoch read from a word in device memory (usv_caps_perturb_dev).
 //   caps_loss_kernel<A>
 //       sac_policy_kernel's shape, from the same two forms (usv_sac.hpp): sac_for_rows with the row's 3 A means in
 //       registers and the two distances as the strand's terms, then sac_finish and its thread's write.
@@ -27,34 +29,22 @@ struct CapsPerturbArgs {
   uint32_t epoch;
 };
 
-__global__ __launch_bounds__(kBlock) void caps_perturb_kernel(CapsPerturbArgs a) {
-  const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
-  if (t >= a.blocks) return;
-  const long long r = t / a.row_blocks;
-  const int b = (int)(t - r * a.row_blocks);
-  const int count = a.W - 4 * b < 4 ? a.W - 4 * b : 4;
-  const long long at = r * a.W + 4 * b;
-  const float* const src = a.obs + at;
-  float* const dst = a.out + at;
-  float z[4];
-  caps_block_normals(a.seed, (uint64_t)r, a.epoch, (uint32_t)b, z);
-  if (count == 4 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
-    float4 v = *reinterpret_cast<const float4*>(src);
-    v.x = caps_near(v.x, a.eps, z[0]);
-    v.y = caps_near(v.y, a.eps, z[1]);
-    v.z = caps_near(v.z, a.eps, z[2]);
-    v.w = caps_near(v.w, a.eps, z[3]);
-    *reinterpret_cast<float4*>(dst) = v;
-    return;
-  }
-  float v[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (q < count) v[q] = src[q];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (q < count) dst[q] = caps_near(v[q], a.eps, z[q]);
-}
+#define USV_NOISE_KERNEL(name) name##_kernel
+#define USV_NOISE_EPOCH_PARAM
+#define USV_NOISE_PROLOGUE
+#include "usv_caps_noise.inc"
+#undef USV_NOISE_KERNEL
+#undef USV_NOISE_EPOCH_PARAM
+#undef USV_NOISE_PROLOGUE
+
+// caps_perturb_dev_kernel (usv_caps_perturb_dev): the epoch is the word epoch_dev points to, read once by each wave.
+#define USV_NOISE_KERNEL(name) name##_dev_kernel
+#define USV_NOISE_EPOCH_PARAM , const uint32_t* __restrict__ epoch_dev
+#define USV_NOISE_PROLOGUE a.epoch = sde_epoch_word(epoch_dev);
+#include "usv_caps_noise.inc"
+#undef USV_NOISE_KERNEL
+#undef USV_NOISE_EPOCH_PARAM
+#undef USV_NOISE_PROLOGUE
 
 struct CapsLossArgs {
   int rows, squash;

@@ -27,6 +27,8 @@
 //   usv_sde.hpp           gSDE heads: one row loop under the three forwards, the two backwards, weights
 //                         (usv_sde_sample / usv_sde_weights / usv_sde_squash_forward / _backward / usv_sde_eval_forward /
 //                         _backward)
+//   usv_sde_noise.inc     the four gSDE kernels that draw noise, stated once and included twice by usv_sde.hpp: with
+//                         the epoch in the arguments, and read from a device word (usv_sde_*_dev)
 //   usv_replay_math.hpp   replay buffer: slots, frame rows, age and live masks, n-step runs (host C++, no HIP)
 //   usv_replay.hpp        ReplayBuffer: frame-deduplicated ring and fused sampling (usv_replay_put_obs / _put_step / _gather /
 //                         _gather_nstep)
@@ -36,9 +38,12 @@
 //                         (usv_sac_critic_loss / _policy_loss / _loss_backward)
 //   usv_caps_math.hpp     CAPS regulariser: counter layout of the perturbation, distances, unit gradients (host C++, no HIP)
 //   usv_caps.hpp          CAPS regulariser: perturbed observations, the fused loss (usv_caps_perturb / usv_caps_loss)
+//   usv_caps_noise.inc    caps_perturb_kernel, stated once and included twice likewise (usv_caps_perturb_dev)
 //   usv_optim_math.hpp    optimizer step: Adam's scalars and element update, the clip, the norm's order (host C++, no HIP)
 //   usv_optim.hpp         kernels over a tensor list: clip_grad_norm_ and Adam (the list passed by value), Polyak (a
-//                         device table), one element loop under both (usv_adam_step / usv_polyak_update)
+//                         device table), one element loop under both (usv_adam_step / usv_polyak_update); Adam with
+//                         its step and lr in a device clock block, and the one-thread counter kernels
+//                         (usv_adam_step_dev / usv_counter_add): what a captured graph can replay
 //   usv_ppo_math.hpp      PPO loss: moments, the row's terms and unit gradients, the finish, explained variance
 //                         (host C++, no HIP)
 //   usv_ppo.hpp           PPO loss: two moment kernels and the fused loss on usv_sac.hpp's reduction
@@ -926,6 +931,24 @@ static int refuse_bufs(const Buf* b, size_t n, int& dev, const char* prefix, con
   return refuse_bufs(b, n, &dev, msg);
 }
 
+// Whether `stream` is recording a graph.  An entry that would synchronise or copy from the host asks first and
+// refuses: during a capture either is an error that also invalidates the capture.
+static bool stream_capturing(void* stream) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return st != hipStreamCaptureStatusNone;
+}
+
+// The device word of a _dev entry `fn` (`what`: "epoch_dev", "word_dev"): not null and 4-B aligned.  No HIP call.
+static int refuse_word(const char* fn, const char* what, const void* word) {
+  if (!word) return fail(USV_ERR_ARG, std::string(fn) + ": null " + what);
+  if ((reinterpret_cast<uintptr_t>(word) & 3) != 0) return fail(USV_ERR_ARG, std::string(fn) + ": " + what + " is not 4-B aligned");
+  return USV_OK;
+}
+
 // The gathers' check of idx and of their outputs out[0 .. n), before the buffers' device is looked at.
 static int refuse_gather_bufs(const char* fn, const int64_t* idx, const Buf* out, size_t n) {
   const std::string p = std::string(fn) + ": ";
@@ -1331,47 +1354,94 @@ static int sde_launch_backward(const usv_sde* s, K k1, K k2, int64_t rows, float
 }
 }  // extern "C++"
 
-int usv_sde_sample(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
-                   const float* std, float* act, float* act_env, float* logp, void* stream) {
+// The four entries that draw noise, each behind its two forms: the epoch an argument (epoch_dev null), or a word in
+// device memory that the kernel reads (the _dev entries; `epoch` is then not used).
+static int sde_sample(const usv_sde* s, uint32_t epoch, const uint32_t* epoch_dev, const float* mean, const float* lat,
+                      size_t stride, const float* std, float* act, float* act_env, float* logp, void* stream) {
   SdeArgs a;
   int dev;
   if (int rc = sde_check(s, epoch, a)) return rc;
   if (int rc = sde_stride(s, stride, "usv_sde_sample")) return rc;
-  const Buf all[] = {{lat, 16}, {mean, 4}, {std, 4}, {act, 4}, {act_env, 4}, {logp, 4}};
-  if (int rc = sde_bufs(all, 6, dev)) return rc;
+  const Buf all[] = {{lat, 16}, {mean, 4}, {std, 4}, {act, 4}, {act_env, 4}, {logp, 4}, {epoch_dev, 4, true}};
+  if (int rc = sde_bufs(all, 7, dev)) return rc;
   DeviceGuard g(dev);
-  return sde_launch(s, sde_sample_kernel<1>, sde_sample_kernel<2>, sde_wave_blocks(a.n), stream, a, mean, lat, stride,
-                    std, act, act_env, logp);
+  const int64_t blocks = sde_wave_blocks(a.n);
+  if (epoch_dev)
+    return sde_launch(s, sde_sample_dev_kernel<1>, sde_sample_dev_kernel<2>, blocks, stream, a, epoch_dev, mean, lat,
+                      stride, std, act, act_env, logp);
+  return sde_launch(s, sde_sample_kernel<1>, sde_sample_kernel<2>, blocks, stream, a, mean, lat, stride, std, act,
+                    act_env, logp);
 }
 
-int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std, float* w, void* stream) {
+int usv_sde_sample(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
+                   const float* std, float* act, float* act_env, float* logp, void* stream) {
+  return sde_sample(s, epoch, nullptr, mean, lat, stride, std, act, act_env, logp, stream);
+}
+
+int usv_sde_sample_dev(const usv_sde* s, const uint32_t* epoch_dev, const float* mean, const float* lat, size_t stride,
+                       const float* std, float* act, float* act_env, float* logp, void* stream) {
+  if (int rc = refuse_word("usv_sde_sample_dev", "epoch_dev", epoch_dev)) return rc;
+  return sde_sample(s, 0u, epoch_dev, mean, lat, stride, std, act, act_env, logp, stream);
+}
+
+static int sde_weights(const usv_sde* s, uint32_t epoch, const uint32_t* epoch_dev, const float* std, float* w,
+                       void* stream) {
   SdeArgs a;
   int dev;
   if (int rc = sde_check(s, epoch, a)) return rc;
   const int64_t threads = (int64_t)a.n * (a.L * s->act_dim / 4);
   if ((threads + kBlock - 1) / kBlock > 2147483647)
     return fail(USV_ERR_ARG, "usv_sde_weights: n * latent_dim * act_dim / 4 is above 2^31 - 1 blocks of 256");
-  const Buf all[] = {{w, 4}, {std, 4}};
-  if (int rc = sde_bufs(all, 2, dev)) return rc;
+  const Buf all[] = {{w, 4}, {std, 4}, {epoch_dev, 4, true}};
+  if (int rc = sde_bufs(all, 3, dev)) return rc;
   DeviceGuard g(dev);
-  return sde_launch(s, sde_weights_kernel<1>, sde_weights_kernel<2>, (threads + kBlock - 1) / kBlock, stream, a, std,
-                    w);
+  const int64_t blocks = (threads + kBlock - 1) / kBlock;
+  if (epoch_dev)
+    return sde_launch(s, sde_weights_dev_kernel<1>, sde_weights_dev_kernel<2>, blocks, stream, a, epoch_dev, std, w);
+  return sde_launch(s, sde_weights_kernel<1>, sde_weights_kernel<2>, blocks, stream, a, std, w);
 }
 
-int usv_sde_squash_forward(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
-                           const float* std, float* act, float* act_env, float* logp, float* gauss, float* var,
-                           void* stream) {
+int usv_sde_weights(const usv_sde* s, uint32_t epoch, const float* std, float* w, void* stream) {
+  return sde_weights(s, epoch, nullptr, std, w, stream);
+}
+
+int usv_sde_weights_dev(const usv_sde* s, const uint32_t* epoch_dev, const float* std, float* w, void* stream) {
+  if (int rc = refuse_word("usv_sde_weights_dev", "epoch_dev", epoch_dev)) return rc;
+  return sde_weights(s, 0u, epoch_dev, std, w, stream);
+}
+
+static int sde_squash_forward(const usv_sde* s, uint32_t epoch, const uint32_t* epoch_dev, const float* mean,
+                              const float* lat, size_t stride, const float* std, float* act, float* act_env,
+                              float* logp, float* gauss, float* var, void* stream) {
   SdeArgs a;
   int dev;
   if (int rc = sde_check(s, epoch, a)) return rc;
   if (int rc = sde_stride(s, stride, "usv_sde_squash_forward")) return rc;
   if ((gauss == nullptr) != (var == nullptr))
     return fail(USV_ERR_ARG, "usv_sde_squash_forward: gauss and var must be both NULL or both set");
-  const Buf all[] = {{lat, 16}, {mean, 4}, {std, 4}, {act, 4}, {act_env, 4}, {logp, 4}, {gauss, 4, true}, {var, 4, true}};
-  if (int rc = sde_bufs(all, 8, dev)) return rc;
+  const Buf all[] = {{lat, 16}, {mean, 4}, {std, 4}, {act, 4}, {act_env, 4}, {logp, 4}, {gauss, 4, true}, {var, 4, true},
+                     {epoch_dev, 4, true}};
+  if (int rc = sde_bufs(all, 9, dev)) return rc;
   DeviceGuard g(dev);
-  return sde_launch(s, sde_squash_forward_kernel<1>, sde_squash_forward_kernel<2>, sde_wave_blocks(a.n), stream, a,
-                    mean, lat, stride, std, act, act_env, logp, gauss, var);
+  const int64_t blocks = sde_wave_blocks(a.n);
+  if (epoch_dev)
+    return sde_launch(s, sde_squash_forward_dev_kernel<1>, sde_squash_forward_dev_kernel<2>, blocks, stream, a,
+                      epoch_dev, mean, lat, stride, std, act, act_env, logp, gauss, var);
+  return sde_launch(s, sde_squash_forward_kernel<1>, sde_squash_forward_kernel<2>, blocks, stream, a, mean, lat, stride,
+                    std, act, act_env, logp, gauss, var);
+}
+
+int usv_sde_squash_forward(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
+                           const float* std, float* act, float* act_env, float* logp, float* gauss, float* var,
+                           void* stream) {
+  return sde_squash_forward(s, epoch, nullptr, mean, lat, stride, std, act, act_env, logp, gauss, var, stream);
+}
+
+int usv_sde_squash_forward_dev(const usv_sde* s, const uint32_t* epoch_dev, const float* mean, const float* lat,
+                               size_t stride, const float* std, float* act, float* act_env, float* logp, float* gauss,
+                               float* var, void* stream) {
+  if (int rc = refuse_word("usv_sde_squash_forward_dev", "epoch_dev", epoch_dev)) return rc;
+  return sde_squash_forward(s, 0u, epoch_dev, mean, lat, stride, std, act, act_env, logp, gauss, var, stream);
 }
 
 size_t usv_sde_squash_scratch_floats(const usv_sde* s) {
@@ -1379,10 +1449,10 @@ size_t usv_sde_squash_scratch_floats(const usv_sde* s) {
   return sde_check(s, 0u, a) ? 0 : sde_scratch_floats(a.n, s);
 }
 
-int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
-                            const float* std, const float* gauss, const float* var, const float* g_act,
-                            const float* g_logp, float* g_mean, float* g_lat, size_t g_stride, float* g_std,
-                            float* scratch, void* stream) {
+static int sde_squash_backward(const usv_sde* s, uint32_t epoch, const uint32_t* epoch_dev, const float* mean,
+                               const float* lat, size_t stride, const float* std, const float* gauss, const float* var,
+                               const float* g_act, const float* g_logp, float* g_mean, float* g_lat, size_t g_stride,
+                               float* g_std, float* scratch, void* stream) {
   SdeArgs a;
   int dev;
   if (int rc = sde_check(s, epoch, a)) return rc;
@@ -1390,12 +1460,34 @@ int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean,
   if (int rc = sde_stride(s, g_stride, "usv_sde_squash_backward", "g_lat ")) return rc;
   if (!scratch) return fail(USV_ERR_ARG, "usv_sde_squash_backward: null scratch");
   const Buf all[] = {{lat, 16},  {g_lat, 16}, {scratch, 16},      {mean, 4},           {std, 4},   {gauss, 4},
-                     {var, 4},   {g_mean, 4}, {g_act, 4, true},   {g_logp, 4, true},   {g_std, 4}};
-  if (int rc = sde_bufs(all, 11, dev)) return rc;
+                     {var, 4},   {g_mean, 4}, {g_act, 4, true},   {g_logp, 4, true},   {g_std, 4}, {epoch_dev, 4, true}};
+  if (int rc = sde_bufs(all, 12, dev)) return rc;
   DeviceGuard g(dev);
+  const int R = (int)sde_rows_per_partial(a.n);
+  if (epoch_dev)
+    return sde_launch_backward(s, sde_squash_backward_dev_kernel<1>, sde_squash_backward_dev_kernel<2>, a.n, scratch,
+                               g_std, stream, a, epoch_dev, R, mean, lat, stride, std, gauss, var, g_act, g_logp, g_mean,
+                               g_lat, g_stride, scratch);
   return sde_launch_backward(s, sde_squash_backward_kernel<1>, sde_squash_backward_kernel<2>, a.n, scratch, g_std,
-                             stream, a, (int)sde_rows_per_partial(a.n), mean, lat, stride, std, gauss, var, g_act, g_logp,
-                             g_mean, g_lat, g_stride, scratch);
+                             stream, a, R, mean, lat, stride, std, gauss, var, g_act, g_logp, g_mean, g_lat, g_stride,
+                             scratch);
+}
+
+int usv_sde_squash_backward(const usv_sde* s, uint32_t epoch, const float* mean, const float* lat, size_t stride,
+                            const float* std, const float* gauss, const float* var, const float* g_act,
+                            const float* g_logp, float* g_mean, float* g_lat, size_t g_stride, float* g_std,
+                            float* scratch, void* stream) {
+  return sde_squash_backward(s, epoch, nullptr, mean, lat, stride, std, gauss, var, g_act, g_logp, g_mean, g_lat,
+                             g_stride, g_std, scratch, stream);
+}
+
+int usv_sde_squash_backward_dev(const usv_sde* s, const uint32_t* epoch_dev, const float* mean, const float* lat,
+                                size_t stride, const float* std, const float* gauss, const float* var,
+                                const float* g_act, const float* g_logp, float* g_mean, float* g_lat, size_t g_stride,
+                                float* g_std, float* scratch, void* stream) {
+  if (int rc = refuse_word("usv_sde_squash_backward_dev", "epoch_dev", epoch_dev)) return rc;
+  return sde_squash_backward(s, 0u, epoch_dev, mean, lat, stride, std, gauss, var, g_act, g_logp, g_mean, g_lat,
+                             g_stride, g_std, scratch, stream);
 }
 
 int usv_sde_eval_forward(const usv_sde* s, int32_t rows, const float* mean, const float* lat, size_t stride,
@@ -1628,22 +1720,38 @@ int usv_sac_loss_backward(int32_t rows, const float* up, const float* g1, const 
 // ---- CAPS regulariser (usv_caps.hpp)
 static int caps_bufs(const Buf* b, size_t nb, int& dev) { return refuse_bufs(b, nb, dev, "usv_caps", "scratch"); }
 
-int usv_caps_perturb(int32_t rows, int32_t width, const float* obs, float* out, float eps, uint64_t seed, uint32_t epoch,
-                     void* stream) {
+// usv_caps_perturb's two forms, as the gSDE entries have them.
+static int caps_perturb(const char* fn, int32_t rows, int32_t width, const float* obs, float* out, float eps,
+                        uint64_t seed, uint32_t epoch, const uint32_t* epoch_dev, void* stream) {
   int dev;
-  if (rows < 1) return fail(USV_ERR_ARG, "usv_caps_perturb: rows must be >= 1");
-  if (width < 1) return fail(USV_ERR_ARG, "usv_caps_perturb: width must be >= 1");
-  if ((int64_t)rows * width > 2147483647) return fail(USV_ERR_ARG, "usv_caps_perturb: rows * width is above 2^31 - 1");
-  if (!caps_weight_ok(eps)) return fail(USV_ERR_ARG, "usv_caps_perturb: eps must be finite and >= 0");
-  const Buf all[] = {{obs, 4}, {out, 4}};
-  if (int rc = caps_bufs(all, 2, dev)) return rc;
+  const std::string p = std::string(fn) + ": ";
+  if (rows < 1) return fail(USV_ERR_ARG, p + "rows must be >= 1");
+  if (width < 1) return fail(USV_ERR_ARG, p + "width must be >= 1");
+  if ((int64_t)rows * width > 2147483647) return fail(USV_ERR_ARG, p + "rows * width is above 2^31 - 1");
+  if (!caps_weight_ok(eps)) return fail(USV_ERR_ARG, p + "eps must be finite and >= 0");
+  const Buf all[] = {{obs, 4}, {out, 4}, {epoch_dev, 4, true}};
+  if (int rc = caps_bufs(all, 3, dev)) return rc;
   DeviceGuard g(dev);
   const int row_blocks = (int)caps_row_blocks(width);
   const CapsPerturbArgs a{(long long)rows * row_blocks, width, row_blocks, obs, out, eps, seed, epoch};
-  hipLaunchKernelGGL(caps_perturb_kernel, dim3((unsigned)((a.blocks + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     (hipStream_t)stream, a);
+  const dim3 grid((unsigned)((a.blocks + kBlock - 1) / kBlock));
+  if (epoch_dev)
+    hipLaunchKernelGGL(caps_perturb_dev_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a, epoch_dev);
+  else
+    hipLaunchKernelGGL(caps_perturb_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return USV_OK;
+}
+
+int usv_caps_perturb(int32_t rows, int32_t width, const float* obs, float* out, float eps, uint64_t seed, uint32_t epoch,
+                     void* stream) {
+  return caps_perturb("usv_caps_perturb", rows, width, obs, out, eps, seed, epoch, nullptr, stream);
+}
+
+int usv_caps_perturb_dev(int32_t rows, int32_t width, const float* obs, float* out, float eps, uint64_t seed,
+                         const uint32_t* epoch_dev, void* stream) {
+  if (int rc = refuse_word("usv_caps_perturb_dev", "epoch_dev", epoch_dev)) return rc;
+  return caps_perturb("usv_caps_perturb_dev", rows, width, obs, out, eps, seed, 0u, epoch_dev, stream);
 }
 
 int usv_caps_loss(int32_t rows, int32_t act_dim, int32_t squash, const float* mean, const float* mean_next,
@@ -1758,25 +1866,33 @@ size_t usv_polyak_table_bytes(const usv_polyak_pair* pairs, int32_t n_pairs) {
   return list_count(kPolyakWords, pairs, n_pairs, true, live, chunks, state).empty() ? polyak_bytes(live, chunks) : 0;
 }
 
-int usv_polyak_update(const usv_polyak_pair* pairs, int32_t n_pairs, void* table, size_t table_bytes, int32_t upload,
-                      double tau, void* stream) {
+// usv_polyak_update (step) and usv_polyak_prepare (the upload alone; tau is then not looked at, nothing is launched).
+static int polyak_call(const char* fn, const usv_polyak_pair* pairs, int32_t n_pairs, void* table, size_t table_bytes,
+                       bool upload, bool step, double tau, void* stream) {
   int64_t live, chunks, state;
   int dev;
-  if (const std::string why = list_count(kPolyakWords, pairs, n_pairs, true, live, chunks, state); !why.empty())
+  const std::string p = std::string(fn) + ": ";
+  ListWords words = kPolyakWords;
+  words.fn = fn;
+  if (const std::string why = list_count(words, pairs, n_pairs, true, live, chunks, state); !why.empty())
     return fail(USV_ERR_ARG, why);
-  if (!polyak_tau_ok(tau)) return fail(USV_ERR_ARG, "usv_polyak_update: tau must be in [0, 1]");
+  if (step && !polyak_tau_ok(tau)) return fail(USV_ERR_ARG, p + "tau must be in [0, 1]");
   if (live == 0) return USV_OK;
-  if (!table) return fail(USV_ERR_ARG, "usv_polyak_update: null table");
-  if ((reinterpret_cast<uintptr_t>(table) & 7) != 0) return fail(USV_ERR_ARG, "usv_polyak_update: the table is not 8-B aligned");
-  if (table_bytes < polyak_bytes(live, chunks)) return fail(USV_ERR_ARG, "usv_polyak_update: the table is too small");
+  if (!table) return fail(USV_ERR_ARG, p + "null table");
+  if ((reinterpret_cast<uintptr_t>(table) & 7) != 0) return fail(USV_ERR_ARG, p + "the table is not 8-B aligned");
+  if (table_bytes < polyak_bytes(live, chunks)) return fail(USV_ERR_ARG, p + "the table is too small");
   std::vector<Buf> bufs = {{table, 8}};
   if (upload) list_bufs(pairs, n_pairs, bufs);
   if (check_bufs(bufs.data(), bufs.size(), &dev) == kBufDevice)
-    return fail(USV_ERR_ARG, dev < 0 ? "usv_polyak_update: the table is not a device pointer"
-                                     : "usv_polyak_update: a tensor is not a device pointer on the table's device");
+    return fail(USV_ERR_ARG, p + (dev < 0 ? "the table is not a device pointer"
+                                          : "a tensor is not a device pointer on the table's device"));
   DeviceGuard g(dev);
   static_assert(sizeof(PolyakPair) == 24 && sizeof(PolyakChunk) == 8, "the table's layout");
   if (upload) {
+    // the upload synchronises and copies from the host: both are errors while the stream records a graph
+    if (step && stream_capturing(stream))
+      return fail(USV_ERR_ARG, p + "the table upload is pending while the stream is capturing: call usv_polyak_prepare "
+                                   "(DevicePolyak.prepare()) before the capture begins");
     std::vector<unsigned char> host(polyak_bytes(live, chunks));
     PolyakPair* const hp = reinterpret_cast<PolyakPair*>(host.data());
     PolyakChunk* const hc = reinterpret_cast<PolyakChunk*>(host.data() + (size_t)live * sizeof(PolyakPair));
@@ -1791,6 +1907,7 @@ int usv_polyak_update(const usv_polyak_pair* pairs, int32_t n_pairs, void* table
     HIP_TRY(hipMemcpy(table, host.data(), host.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());
   }
+  if (!step) return USV_OK;
   float tau_f, om;
   polyak_coeffs(tau, tau_f, om);
   const PolyakPair* const dp = (const PolyakPair*)table;
@@ -1798,6 +1915,15 @@ int usv_polyak_update(const usv_polyak_pair* pairs, int32_t n_pairs, void* table
   hipLaunchKernelGGL(polyak_kernel, dim3((unsigned)chunks), dim3(kBlock), 0, (hipStream_t)stream, dp, dc, tau_f, om);
   HIP_TRY(hipGetLastError());
   return USV_OK;
+}
+
+int usv_polyak_update(const usv_polyak_pair* pairs, int32_t n_pairs, void* table, size_t table_bytes, int32_t upload,
+                      double tau, void* stream) {
+  return polyak_call("usv_polyak_update", pairs, n_pairs, table, table_bytes, upload != 0, true, tau, stream);
+}
+
+int usv_polyak_prepare(const usv_polyak_pair* pairs, int32_t n_pairs, void* table, size_t table_bytes) {
+  return polyak_call("usv_polyak_prepare", pairs, n_pairs, table, table_bytes, true, false, 0.0, nullptr);
 }
 
 size_t usv_adam_state_floats(const usv_adam_tensor* tensors, int32_t n) {
@@ -1810,36 +1936,51 @@ size_t usv_adam_scratch_floats(const usv_adam_tensor* tensors, int32_t n) {
   return list_count(kAdamWords, tensors, n, false, live, chunks, state).empty() ? optim_scratch_floats(chunks) : 0;
 }
 
-int usv_adam_step(const usv_adam_tensor* tensors, int32_t n, float* m, float* v, size_t state_floats, int64_t step,
-                  double lr, double beta1, double beta2, double eps, double max_grad_norm, float* scratch,
-                  size_t scratch_floats, float* norm_out, void* stream) {
+size_t usv_adam_clock_bytes(void) { return sizeof(AdamClock); }
+
+// usv_adam_step (clock null: `step` and `lr` are the caller's) and usv_adam_step_dev (they live in the clock block).
+static int adam_step(const char* fn, const usv_adam_tensor* tensors, int32_t n, float* m, float* v, size_t state_floats,
+                     int64_t step, double lr, void* clock, double beta1, double beta2, double eps,
+                     double max_grad_norm, float* scratch, size_t scratch_floats, float* norm_out, void* stream) {
   int64_t live, chunks, state;
   int dev;
-  if (const std::string why = list_count(kAdamWords, tensors, n, true, live, chunks, state); !why.empty())
+  const std::string p = std::string(fn) + ": ";
+  const bool host_clock = clock == nullptr;
+  ListWords words = kAdamWords;
+  words.fn = fn;
+  if (const std::string why = list_count(words, tensors, n, true, live, chunks, state); !why.empty())
     return fail(USV_ERR_ARG, why);
-  if (step < 1) return fail(USV_ERR_ARG, "usv_adam_step: step must be >= 1");
-  if (!adam_rate_ok(lr)) return fail(USV_ERR_ARG, "usv_adam_step: lr must be finite and >= 0");
-  if (!adam_rate_ok(eps)) return fail(USV_ERR_ARG, "usv_adam_step: eps must be finite and >= 0");
-  if (!adam_beta_ok(beta1) || !adam_beta_ok(beta2)) return fail(USV_ERR_ARG, "usv_adam_step: the betas must be in [0, 1)");
-  if (max_grad_norm != max_grad_norm) return fail(USV_ERR_ARG, "usv_adam_step: max_grad_norm is NaN");
+  if (host_clock && step < 1) return fail(USV_ERR_ARG, p + "step must be >= 1");
+  if (host_clock && !adam_rate_ok(lr)) return fail(USV_ERR_ARG, p + "lr must be finite and >= 0");
+  if (!adam_rate_ok(eps)) return fail(USV_ERR_ARG, p + "eps must be finite and >= 0");
+  if (!adam_beta_ok(beta1) || !adam_beta_ok(beta2)) return fail(USV_ERR_ARG, p + "the betas must be in [0, 1)");
+  if (max_grad_norm != max_grad_norm) return fail(USV_ERR_ARG, p + "max_grad_norm is NaN");
   const bool clip = max_grad_norm >= 0.0;
-  if (clip && !norm_out) return fail(USV_ERR_ARG, "usv_adam_step: clipping needs norm_out");
-  if (!m || !v) return fail(USV_ERR_ARG, "usv_adam_step: null state");
-  if (clip && !scratch) return fail(USV_ERR_ARG, "usv_adam_step: clipping needs scratch");
-  if (state_floats < (size_t)state) return fail(USV_ERR_ARG, "usv_adam_step: the state is too small");
-  if (clip && scratch_floats < optim_scratch_floats(chunks)) return fail(USV_ERR_ARG, "usv_adam_step: the scratch is too small");
-  std::vector<Buf> bufs = {{m, 16}, {v, 16}, {clip ? scratch : nullptr, 16, true}, {clip ? norm_out : nullptr, 4, true}};
-  bufs.reserve(4 + 2 * (size_t)live);
+  if (clip && !norm_out) return fail(USV_ERR_ARG, p + "clipping needs norm_out");
+  if (!m || !v) return fail(USV_ERR_ARG, p + "null state");
+  if (clip && !scratch) return fail(USV_ERR_ARG, p + "clipping needs scratch");
+  if (state_floats < (size_t)state) return fail(USV_ERR_ARG, p + "the state is too small");
+  if (clip && scratch_floats < optim_scratch_floats(chunks)) return fail(USV_ERR_ARG, p + "the scratch is too small");
+  std::vector<Buf> bufs = {{m, 16}, {v, 16}, {clip ? scratch : nullptr, 16, true}, {clip ? norm_out : nullptr, 4, true},
+                           {clock, 16, true}};
+  bufs.reserve(5 + 2 * (size_t)live);
   list_bufs(tensors, n, bufs);
-  static const char* const msg[4] = {"usv_adam_step: null state",
-                                     "usv_adam_step: state or scratch is not 16-B aligned or norm_out is not 4-B aligned",
-                                     "usv_adam_step: the state is not a device pointer",
-                                     "usv_adam_step: a buffer is not a device pointer on the state's device"};
+  const std::string null = p + "null state",
+                    align = p + "state, scratch or the clock block is not 16-B aligned or norm_out is not 4-B aligned",
+                    first = p + "the state is not a device pointer",
+                    other = p + "a buffer is not a device pointer on the state's device";
+  const char* const msg[4] = {null.c_str(), align.c_str(), first.c_str(), other.c_str()};
   if (int rc = refuse_bufs(bufs.data(), bufs.size(), nullptr, msg)) return rc;
   if (live == 0) return USV_OK;
   if (int rc = refuse_bufs(bufs.data(), bufs.size(), &dev, msg)) return rc;
   DeviceGuard g(dev);
-  const AdamScalars sc = adam_scalars(step, lr, beta1, beta2, eps);
+  // with a clock block: one launch ahead of the passes moves the step on and derives its scalars, once however many
+  // launches the list takes; the scalars below that depend on the step are then not read
+  const AdamScalars sc = adam_scalars(host_clock ? step : 1, host_clock ? lr : 0.0, beta1, beta2, eps);
+  if (!host_clock) {
+    hipLaunchKernelGGL(adam_clock_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (AdamClock*)clock, beta1, beta2);
+    HIP_TRY(hipGetLastError());
+  }
   if (clip) {
     list_pass(tensors, n, [&](const TensorTable& tab, dim3 grid) {
       const OptimSqsumArgs a{tab, (int)chunks, scratch, norm_out};
@@ -1848,9 +1989,43 @@ int usv_adam_step(const usv_adam_tensor* tensors, int32_t n, float* m, float* v,
     HIP_TRY(hipGetLastError());
   }
   list_pass(tensors, n, [&](const TensorTable& tab, dim3 grid) {
-    const OptimAdamArgs a{tab, m, v, clip ? norm_out : nullptr, (float)max_grad_norm, sc};
-    hipLaunchKernelGGL(optim_adam_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+    if (host_clock) {
+      const OptimAdamArgs a{tab, m, v, clip ? norm_out : nullptr, (float)max_grad_norm, sc};
+      hipLaunchKernelGGL(optim_adam_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+    } else {
+      const OptimAdamDevArgs a{tab, m, v, clip ? norm_out : nullptr, (float)max_grad_norm, sc, (const AdamClock*)clock};
+      hipLaunchKernelGGL(optim_adam_dev_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, a);
+    }
   });
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+int usv_adam_step(const usv_adam_tensor* tensors, int32_t n, float* m, float* v, size_t state_floats, int64_t step,
+                  double lr, double beta1, double beta2, double eps, double max_grad_norm, float* scratch,
+                  size_t scratch_floats, float* norm_out, void* stream) {
+  return adam_step("usv_adam_step", tensors, n, m, v, state_floats, step, lr, nullptr, beta1, beta2, eps,
+                   max_grad_norm, scratch, scratch_floats, norm_out, stream);
+}
+
+int usv_adam_step_dev(const usv_adam_tensor* tensors, int32_t n, float* m, float* v, size_t state_floats,
+                      void* clock_dev, size_t clock_bytes, double beta1, double beta2, double eps, double max_grad_norm,
+                      float* scratch, size_t scratch_floats, float* norm_out, void* stream) {
+  if (!clock_dev) return fail(USV_ERR_ARG, "usv_adam_step_dev: null clock block");
+  if ((reinterpret_cast<uintptr_t>(clock_dev) & 15) != 0)
+    return fail(USV_ERR_ARG, "usv_adam_step_dev: the clock block is not 16-B aligned");
+  if (clock_bytes < sizeof(AdamClock)) return fail(USV_ERR_ARG, "usv_adam_step_dev: the clock block is too small");
+  return adam_step("usv_adam_step_dev", tensors, n, m, v, state_floats, 0, 0.0, clock_dev, beta1, beta2,
+                   eps, max_grad_norm, scratch, scratch_floats, norm_out, stream);
+}
+
+int usv_counter_add(uint32_t* word_dev, uint32_t inc, void* stream) {
+  int dev;
+  if (int rc = refuse_word("usv_counter_add", "word_dev", word_dev)) return rc;
+  const Buf all[] = {{word_dev, 4}};
+  if (check_bufs(all, 1, &dev) != kBufOk) return fail(USV_ERR_ARG, "usv_counter_add: word_dev is not a device pointer");
+  DeviceGuard g(dev);
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, word_dev, inc);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

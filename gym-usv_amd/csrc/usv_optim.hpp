@@ -20,6 +20,10 @@
 //   optim_adam_kernel    coef from the norm (with clipping), then one read each of p, g, m, v and one write each of
 //                        p, m, v per element, wide where p and g are both 16-B aligned.  The state segments are
 //                        always 16-B aligned.
+//   optim_adam_dev_kernel  the same pass (optim_adam_chunk) with step_size and bc2_sqrt read from the clock block in
+//                        device memory, which adam_clock_tick_kernel (one thread, one launch per step) advanced and
+//                        derived just before: a captured graph replays a step that counts.
+//   counter_add_kernel   one thread adds to a uint32 in device memory: the noise epoch of a capturable head.
 //   polyak_kernel        a block per chunk of one tensor pair, found through the device table of pairs and the table
 //                        of (pair, chunk) per block: one read of src and dst and one write of dst per element, wide
 //                        where both are 16-B aligned.
@@ -56,7 +60,16 @@ struct OptimAdamArgs {
   AdamScalars s;
 };
 
-static_assert(sizeof(OptimSqsumArgs) <= 3584 && sizeof(OptimAdamArgs) <= 3584,
+struct OptimAdamDevArgs {                             // OptimAdamArgs with the clock block behind it
+  TensorTable tab;
+  float *m, *v;
+  const float* total;
+  float max_norm;
+  AdamScalars s;                                     // step_size and bc2_sqrt are the clock's, not these
+  const AdamClock* clock;
+};
+
+static_assert(sizeof(OptimSqsumArgs) <= 3584 && sizeof(OptimAdamArgs) <= 3584 && sizeof(OptimAdamDevArgs) <= 3584,
               "the arguments and the hidden ones stay under HIP's 4 KiB");
 
 // Polyak's device table: the pairs that hold elements, then a (pair, chunk) per block.
@@ -152,7 +165,9 @@ __global__ __launch_bounds__(kBlock) void optim_sqsum_kernel(OptimSqsumArgs a) {
   if (sac_finish(s, (size_t)(a.tab.first[0] + (int)blockIdx.x), a.chunks, 1, a.scratch)) a.norm_out[0] = optim_norm(s[0]);
 }
 
-__global__ __launch_bounds__(kBlock) void optim_adam_kernel(OptimAdamArgs a) {
+// The Adam pass of a block's chunk under both kernels: `scalars(a)` is the step's AdamScalars.
+template <class Args, class Scalars>
+__device__ __forceinline__ void optim_adam_chunk(const Args& a, Scalars&& scalars) {
   long long off;
   int count;
   const int t = table_find(a.tab, off, count);
@@ -160,11 +175,44 @@ __global__ __launch_bounds__(kBlock) void optim_adam_kernel(OptimAdamArgs a) {
   const float coef = clip ? adam_clip_coef(a.total[0], a.max_norm) : 1.0f;
   float* const p = a.tab.p[t] + off;
   const float* const g = a.tab.g[t] + off;
-  const AdamScalars s = a.s;
+  const AdamScalars s = scalars(a);
   chunk_elements({p, a.m + a.tab.state[t] + off, a.v + a.tab.state[t] + off}, {g}, count, both_wide(p, g),
                  [&](float (&x)[3], const float (&y)[1]) {
                    adam_value(x[0], x[1], x[2], clip ? adam_clipped(y[0], coef) : y[0], s);
                  });
+}
+
+__global__ __launch_bounds__(kBlock) void optim_adam_kernel(OptimAdamArgs a) {
+  optim_adam_chunk(a, [](const OptimAdamArgs& x) { return x.s; });
+}
+
+// usv_adam_step_dev's: step_size and bc2_sqrt come from the clock block, which adam_clock_tick_kernel wrote in the
+// launch before this pass (stream order); a block reads the two words once, wave-uniform.
+__global__ __launch_bounds__(kBlock) void optim_adam_dev_kernel(OptimAdamDevArgs a) {
+  optim_adam_chunk(a, [](const OptimAdamDevArgs& x) {
+    AdamScalars s = x.s;
+    s.step_size = x.clock->step_size;
+    s.bc2_sqrt = x.clock->bc2_sqrt;
+    return s;
+  });
+}
+
+// One thread: the step moves on by one and its two scalars are derived from it and lr, in double, each cast once.
+// Once per usv_adam_step_dev, ahead of its other launches, however many launches the list takes.
+__global__ void adam_clock_tick_kernel(AdamClock* __restrict__ clock, double beta1, double beta2) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t t = clock->step + 1;
+  float step_size, bc2_sqrt;
+  adam_clock_scalars(t, clock->lr, beta1, beta2, step_size, bc2_sqrt);
+  clock->step = t;
+  clock->step_size = step_size;
+  clock->bc2_sqrt = bc2_sqrt;
+}
+
+// One thread: *word += inc, wrapping (usv_counter_add: a noise epoch that lives in device memory).
+__global__ void counter_add_kernel(uint32_t* __restrict__ word, uint32_t inc) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  word[0] = counter_added(word[0], inc);
 }
 
 __global__ __launch_bounds__(kBlock) void polyak_kernel(const PolyakPair* __restrict__ pairs,

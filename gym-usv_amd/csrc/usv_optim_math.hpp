@@ -71,6 +71,28 @@ inline AdamScalars adam_scalars(int64_t t, double lr, double beta1, double beta2
   return s;
 }
 
+// The clock block of usv_adam_step_dev: the step number and lr in device memory, and the two scalars that depend on
+// them, derived on the device once per step (adam_clock_scalars) before any element is updated.  16-B aligned.
+struct alignas(16) AdamClock {
+  double lr;
+  int64_t step;                                      // the number of the last step taken; 0 before the first
+  float step_size, bc2_sqrt;                         // of that step
+  uint32_t reserved[2];
+};
+static_assert(sizeof(AdamClock) == 32, "the clock block's layout (gym_usv_amd/optim.py reads it)");
+
+// adam_scalars's two step-dependent scalars where the device derives them: the same doubles, each cast once.  The
+// device's pow is another library than the host's: a pow off in its last place moves a cast by at most one f32 ulp.
+USV_SAC_HD void adam_clock_scalars(int64_t t, double lr, double beta1, double beta2, float& step_size, float& bc2_sqrt) {
+  const double bc1 = 1.0 - pow(beta1, (double)t);
+  const double bc2 = 1.0 - pow(beta2, (double)t);
+  step_size = (float)(lr / bc1);
+  bc2_sqrt = (float)sqrt(bc2);
+}
+
+// A noise epoch moved on by inc: a uint32 that wraps, as the host's `epoch` does.
+USV_SAC_HD uint32_t counter_added(uint32_t word, uint32_t inc) { return word + inc; }
+
 USV_SAC_HD float optim_norm(float sqsum) { return sqrtf(sqsum); }
 
 USV_SAC_HD float adam_clip_coef(float total, float max_norm) {

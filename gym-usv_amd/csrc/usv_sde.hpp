@@ -19,6 +19,11 @@
 //   sde_squash_backward_kernel<A>, sde_eval_backward_kernel<A>, sde_std_finalise_kernel (adds the partials)
 //   sde_weights_kernel<A>  a lane per block of four elements: w[e][j][k], SB3's exploration_mat, for
 //                          inspection, tests and checkpoints.
+//   sde_sample_dev_kernel<A>, sde_squash_forward_dev_kernel<A>, sde_squash_backward_dev_kernel<A>,
+//   sde_weights_dev_kernel<A>
+//                          the four that draw noise, with the epoch read from a word in device memory instead of
+//                          the arguments (usv_sde_*_dev): the same text (usv_sde_noise.inc), a scalar load per wave
+//                          in front.
 // The [L][A] std table is read once per wave, straight into registers: each element is used by one lane
 // of the wave, once, so staging it in LDS would add a write, a barrier and a read without saving a load;
 // the table (2 KiB at L = 256, A = 2) stays in L2 for the waves of the other envs.
@@ -88,62 +93,30 @@ __device__ __forceinline__ void sde_row_sums(int L, int l, const float* __restri
   }
 }
 
-template <int A>
-__global__ __launch_bounds__(kBlock) void sde_sample_kernel(SdeArgs a, const float* __restrict__ mean,
-                                                           const float* __restrict__ lat, size_t stride,
-                                                           const float* __restrict__ std, float* __restrict__ act,
-                                                           float* __restrict__ act_env, float* __restrict__ logp) {
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int l = lane_id();
-  const int64_t e = (int64_t)blockIdx.x * kWaves + wave;
-  if (e >= a.n) return;                                 // wave-uniform
-  float noise[A], var[A];
-  sde_row_sums<A, true>(a.L, l, lat + (size_t)e * stride, std, a.seed, a.gid0 + (uint64_t)e, a.epoch, noise, var);
-  if (l != 0) return;
-  float lp = 0.0f;
-#pragma unroll
-  for (int k = 0; k < A; ++k) {
-    const float m = mean[(size_t)e * A + k];
-    const float ak = sde_action(m, noise[k]);
-    act[(size_t)e * A + k] = ak;
-    act_env[(size_t)e * A + k] = sde_clip(ak, a.low[k], a.high[k]);
-    lp = lp + sde_logp_term(ak, m, var[k]);
-  }
-  logp[e] = lp;
+// The epoch of a _dev kernel: the word in device memory, read once by each wave (a scalar load: the address is
+// wave-uniform and nothing in the kernel writes it).
+__device__ __forceinline__ uint32_t sde_epoch_word(const uint32_t* __restrict__ epoch_dev) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)epoch_dev[0]);
 }
 
-// The squashed head's forward: the tanh tail.  gauss and var (the backward's saved u and var_k) are NULL together
-// on a call that will not be differentiated.
-template <int A>
-__global__ __launch_bounds__(kBlock) void sde_squash_forward_kernel(SdeArgs a, const float* __restrict__ mean,
-                                                                   const float* __restrict__ lat, size_t stride,
-                                                                   const float* __restrict__ std, float* __restrict__ act,
-                                                                   float* __restrict__ act_env, float* __restrict__ logp,
-                                                                   float* __restrict__ gauss, float* __restrict__ var_out) {
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int l = lane_id();
-  const int64_t e = (int64_t)blockIdx.x * kWaves + wave;
-  if (e >= a.n) return;                                 // wave-uniform
-  float noise[A], var[A];
-  sde_row_sums<A, true>(a.L, l, lat + (size_t)e * stride, std, a.seed, a.gid0 + (uint64_t)e, a.epoch, noise, var);
-  if (l != 0) return;
-  float lp = 0.0f;
-#pragma unroll
-  for (int k = 0; k < A; ++k) {
-    const float m = mean[(size_t)e * A + k];
-    const float u = sde_action(m, noise[k]);
-    float t, om;
-    sde_squash(u, t, om);
-    act[(size_t)e * A + k] = t;
-    act_env[(size_t)e * A + k] = sde_unscale(t, a.low[k], a.high[k]);
-    if (gauss) {
-      gauss[(size_t)e * A + k] = u;
-      var_out[(size_t)e * A + k] = var[k];
-    }
-    lp = lp + sde_squash_logp_term(u, m, var[k], om);
-  }
-  logp[e] = lp;
-}
+// sde_sample_kernel<A>, sde_squash_forward_kernel<A>, sde_squash_backward_kernel<A>, sde_weights_kernel<A>: the epoch
+// is SdeArgs's.
+#define USV_NOISE_KERNEL(name) name##_kernel
+#define USV_NOISE_EPOCH_PARAM
+#define USV_NOISE_PROLOGUE
+#include "usv_sde_noise.inc"
+#undef USV_NOISE_KERNEL
+#undef USV_NOISE_EPOCH_PARAM
+#undef USV_NOISE_PROLOGUE
+
+// ... and their _dev_kernel forms (usv_sde_*_dev): the epoch is the word epoch_dev points to.
+#define USV_NOISE_KERNEL(name) name##_dev_kernel
+#define USV_NOISE_EPOCH_PARAM const uint32_t* __restrict__ epoch_dev,
+#define USV_NOISE_PROLOGUE a.epoch = sde_epoch_word(epoch_dev);
+#include "usv_sde_noise.inc"
+#undef USV_NOISE_KERNEL
+#undef USV_NOISE_EPOCH_PARAM
+#undef USV_NOISE_PROLOGUE
 
 // PPO's evaluate_actions, forward: stored actions under the current policy, no noise.  Lane 0's tail: logp, and
 // with old / adv the ratio and the clipped surrogate.  var_out (the backward's saved var) is NULL on a call that
@@ -173,66 +146,6 @@ __global__ __launch_bounds__(kBlock) void sde_eval_forward_kernel(
     float r;
     sur[e] = sde_ppo_surrogate(lp, old[e], adv[e], clip, r);
     ratio[e] = r;
-  }
-}
-
-// The squashed head's backward.  A wave owns partial p of g_std: rows [p R, min(n, (p + 1) R)), R =
-// sde_rows_per_partial(n).  Pass-outer, row-inner: within a pass of 256 latents a lane keeps the 4 A std values
-// and 4 A g_std accumulators of its elements in registers at any L, walks the partial's rows in ascending order,
-// rebuilds each row's normals as the forward did, stores its four g_lat values with one 16-B store and adds its
-// terms of g_std; then it stores the 4 A partial sums to scratch [P][L][A].  The price: the row tail (G, gn, gv:
-// two exp, a tanh, a few divisions, wave-uniform) is recomputed in every pass.  Lane 0 stores g_mean in its
-// first pass.  No lane waits for another; a lane at or past L stores nothing.
-template <int A>
-__global__ __launch_bounds__(kBlock) void sde_squash_backward_kernel(
-    SdeArgs a, int R, const float* __restrict__ mean, const float* __restrict__ lat, size_t stride,
-    const float* __restrict__ std, const float* __restrict__ gauss, const float* __restrict__ var,
-    const float* __restrict__ g_act, const float* __restrict__ g_logp, float* __restrict__ g_mean,
-    float* __restrict__ g_lat, size_t g_stride, float* __restrict__ part) {
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int l = lane_id();
-  const int64_t p = (int64_t)blockIdx.x * kWaves + wave;
-  const int64_t e0 = p * R;
-  if (e0 >= a.n) return;                                // wave-uniform
-  const int64_t e1 = e0 + R < a.n ? e0 + R : a.n;
-  for (int j0 = kSdePerLane * l; j0 < a.L; j0 += kSdePass) {
-    float s[4 * A], gs[4 * A];
-#pragma unroll
-    for (int i = 0; i < 4 * A; ++i) {
-      s[i] = std[(size_t)j0 * A + i];
-      gs[i] = 0.0f;
-    }
-    for (int64_t e = e0; e < e1; ++e) {
-      const float gl = g_logp ? g_logp[e] : 0.0f;
-      float gn[A], gv[A];
-#pragma unroll
-      for (int k = 0; k < A; ++k) {
-        const size_t at = (size_t)e * A + k;
-        float G;
-        sde_squash_grad_tail(gauss[at], mean[at], var[at], g_act ? g_act[at] : 0.0f, gl, G, gn[k], gv[k]);
-        if (j0 == 0) g_mean[at] = G;                    // lane 0, first pass
-      }
-      const float4 lv = *reinterpret_cast<const float4*>(lat + (size_t)e * stride + j0);
-      const float x[4] = {lv.x, lv.y, lv.z, lv.w};
-      float gx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int m = 0; m < A; ++m) {
-        uint32_t o[4];
-        float z[4];
-        sde_block(a.seed, a.gid0 + (uint64_t)e, a.epoch, (uint32_t)(j0 / 4) * A + m, o);
-        sde_normals(o, z);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int i = 4 * m + q;
-          sde_grad_accum(x[i / A], s[i], z[q], gn[i % A], gv[i % A], gx[i / A], gs[i]);
-        }
-      }
-      *reinterpret_cast<float4*>(g_lat + (size_t)e * g_stride + j0) = make_float4(gx[0], gx[1], gx[2], gx[3]);
-    }
-    float* const dst = part + ((size_t)p * a.L + j0) * A;     // 16-B aligned: scratch is, and (p L + j0) A % 4 == 0
-#pragma unroll
-    for (int m = 0; m < A; ++m)
-      *reinterpret_cast<float4*>(dst + 4 * m) = make_float4(gs[4 * m], gs[4 * m + 1], gs[4 * m + 2], gs[4 * m + 3]);
   }
 }
 
@@ -304,24 +217,6 @@ __global__ __launch_bounds__(kBlock) void sde_std_finalise_kernel(int P, int LA,
   if (sl == 0) sums[w][ie] = acc;
   __syncthreads();
   if (threadIdx.x < 16 && i < LA) g_std[i] = (sums[0][ie] + sums[1][ie]) + (sums[2][ie] + sums[3][ie]);
-}
-
-// blocks_per_env = L * A / 4; thread t of the grid owns block t % blocks_per_env of env t / blocks_per_env.
-template <int A>
-__global__ __launch_bounds__(kBlock) void sde_weights_kernel(SdeArgs a, const float* __restrict__ std,
-                                                            float* __restrict__ w) {
-  const int bpe = a.L * A / 4;
-  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (t >= (int64_t)a.n * bpe) return;
-  const int64_t e = t / bpe;
-  const uint32_t b = (uint32_t)(t - e * bpe);
-  uint32_t o[4];
-  float z[4];
-  sde_block(a.seed, a.gid0 + (uint64_t)e, a.epoch, b, o);
-  sde_normals(o, z);
-  float* const dst = w + (size_t)e * a.L * A + 4 * (size_t)b;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) dst[q] = sde_weight(std[4 * (size_t)b + q], z[q]);
 }
 
 }  // namespace usv

@@ -21,11 +21,12 @@ from .sac import CriticLoss, DevicePolyak, DeviceSACLoss, PolicyLoss  # noqa: F4
 from .caps import DeviceCAPS, SmoothLoss  # noqa: F401
 from .optim import DeviceAdam  # noqa: F401
 from .ppo import DevicePPOLoss, PPOLoss  # noqa: F401
+from .graph import CapturedStep, capture_step  # noqa: F401
 
 __all__ = ["make", "make_vec", "make_sb3_vec_env", "registry", "UsvVectorEnv", "UsvLibError", "ENV_SPECS",
            "DeviceRollout", "DeviceSDE", "DeviceReplay", "ReplaySamples", "NStepReplaySamples",
            "DeviceSACLoss", "DevicePolyak", "CriticLoss", "PolicyLoss", "DeviceCAPS", "SmoothLoss", "DeviceAdam",
-           "DevicePPOLoss", "PPOLoss"]
+           "DevicePPOLoss", "PPOLoss", "capture_step", "CapturedStep"]
 
 registry = {k: {"entry_point": f"gym_usv_amd.envs:{cls}", "max_episode_steps": v[1] or None}
             for (k, v), cls in zip(ENV_SPECS.items(), ("UsvSimpleEnv", "UsvSimpleASMCEnv", "UsvAsmcEnv",

@@ -216,6 +216,18 @@ SIGNATURES = [
     ("usv_ppo_loss", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp]),
     ("usv_ppo_explained_variance", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_counter_add", ctypes.c_int, [_vp, _u32, _vp]),
+    ("usv_sde_sample_dev", ctypes.c_int, [ctypes.POINTER(UsvSde), _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    ("usv_sde_weights_dev", ctypes.c_int, [ctypes.POINTER(UsvSde), _vp, _vp, _vp, _vp]),
+    ("usv_sde_squash_forward_dev", ctypes.c_int, [ctypes.POINTER(UsvSde), _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp]),
+    ("usv_sde_squash_backward_dev", ctypes.c_int, [ctypes.POINTER(UsvSde), _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("usv_caps_perturb_dev", ctypes.c_int, [_i32, _i32, _vp, _vp, _f32, _u64, _vp, _vp]),
+    ("usv_adam_clock_bytes", _sz, []),
+    ("usv_adam_step_dev", ctypes.c_int, [ctypes.POINTER(UsvAdamTensor), _i32, _vp, _vp, _sz, _vp, _sz, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _sz, _vp, _vp]),
+    ("usv_polyak_prepare", ctypes.c_int, [ctypes.POINTER(UsvPolyakPair), _i32, _vp, _sz]),
 ]
 
 _LIBS = {}
@@ -266,6 +278,17 @@ def stream_ptr(device):
     """The current stream of ``device`` as the ``void* stream`` of the C entries."""
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def word_read(word):
+    """The uint32 a one-element int32 device tensor holds (a capturable object's noise epoch): a host sync."""
+    return int(word.item()) & 0xFFFFFFFF
+
+
+def word_write(word, value):
+    """``value`` mod 2^32 into the one-element int32 device tensor ``word``: a stream-ordered write."""
+    value = int(value) & 0xFFFFFFFF
+    word.fill_(value - (1 << 32) if value >= 1 << 31 else value)
 
 
 def cuda_device(device, who):

@@ -31,6 +31,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from .optim import refuse_capture
 
 SmoothLoss = collections.namedtuple("SmoothLoss", "loss temporal spatial")
 MAX_ACT_DIM = 8
@@ -100,9 +101,17 @@ class DeviceCAPS:
     [0, 2^64); pass one different from the env's and from the gSDE heads'.  ``lambda_t``, ``lambda_s``, ``eps_s``:
     finite and >= 0 (``eps_s`` is a standard deviation).  ``squash``: pi = tanh(mean).  ``epoch`` (readable and
     settable, a uint32 that wraps): the noise epoch; save and restore it with a checkpoint.  The object owns a small
-    scratch buffer that grows with the batch: calls of one object must be stream-ordered."""
+    scratch buffer that grows with the batch: calls of one object must be stream-ordered.
 
-    def __init__(self, device, seed, lambda_t=10.0, lambda_s=5.0, eps_s=0.1, squash=True, lib_path=None):
+    ``capturable=True``: the epoch is a word in device memory that ``near``'s kernel reads (``usv_caps_perturb_dev``),
+    so ``near`` is legal inside ``torch.cuda.graph`` and a replay draws the noise of the epoch the word then holds.
+    ``reset_noise()`` is one launch of one thread (``usv_counter_add``), to be captured with the rest; setting ``epoch``
+    is a stream-ordered write and reading it is **a host sync**.  In the default form ``near`` raises ``RuntimeError``
+    while the stream is capturing: a graph would freeze its epoch.  ``loss`` draws no noise and is capturable in
+    both forms, once a warm-up call has grown the scratch to the batch."""
+
+    def __init__(self, device, seed, lambda_t=10.0, lambda_s=5.0, eps_s=0.1, squash=True, lib_path=None,
+                 capturable=False):
         self.lambda_t, self.lambda_s = check_weight("lambda_t", lambda_t), check_weight("lambda_s", lambda_s)
         self.eps_s = check_weight("eps_s", eps_s)
         seed = int(seed)
@@ -111,20 +120,30 @@ class DeviceCAPS:
         self.seed, self.squash = seed, bool(squash)
         self.device = _lib.cuda_device(device, "DeviceCAPS")
         self.lib = _lib.load(lib_path)
+        self.capturable = bool(capturable)
         self._epoch = 0
+        self._word = torch.zeros(1, dtype=torch.int32, device=self.device) if self.capturable else None
         self._scratch, self._scratch_rows = None, 0
 
     @property
     def epoch(self):
-        return self._epoch
+        return self._epoch if self._word is None else _lib.word_read(self._word)
 
     @epoch.setter
     def epoch(self, v):
-        self._epoch = int(v) & 0xFFFFFFFF
+        if self._word is None:
+            self._epoch = int(v) & 0xFFFFFFFF
+        else:
+            refuse_capture("DeviceCAPS.epoch was set", "set it outside the captured region")
+            _lib.word_write(self._word, v)
 
     def reset_noise(self):
-        """New noise for the next ``near``: the epoch moves on, nothing runs on the device."""
-        self.epoch = self._epoch + 1
+        """New noise for the next ``near``: the epoch moves on.  Nothing runs on the device; with ``capturable=True``
+        one launch of one thread."""
+        if self._word is None:
+            self.epoch = self._epoch + 1
+        else:
+            _lib.check(self.lib.usv_counter_add(self._word.data_ptr(), 1, _lib.stream_ptr(self.device)), self.lib)
 
     def _fresh(self, n):
         return torch.empty(n, dtype=torch.float32, device=self.device)
@@ -149,8 +168,14 @@ class DeviceCAPS:
             out = self._fresh(obs.shape)
         else:
             _lib.check_tensor("out", out, torch.float32, (B, W), self.device)
-        _lib.check(self.lib.usv_caps_perturb(B, W, obs.data_ptr(), out.data_ptr(), self.eps_s, self.seed, self._epoch,
-                                             _lib.stream_ptr(self.device)), self.lib)
+        if self._word is None:
+            refuse_capture("DeviceCAPS.near() of a default (capturable=False) object was called",
+                           "its noise epoch is a kernel argument that a graph would freeze; make it with capturable=True")
+            fn, epoch = self.lib.usv_caps_perturb, self._epoch
+        else:
+            fn, epoch = self.lib.usv_caps_perturb_dev, self._word.data_ptr()
+        _lib.check(fn(B, W, obs.data_ptr(), out.data_ptr(), self.eps_s, self.seed, epoch, _lib.stream_ptr(self.device)),
+                   self.lib)
         return out
 
     def _loss(self, mean, mean_next, mean_near, g_mean, g_next, g_near):

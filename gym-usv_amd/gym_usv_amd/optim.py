@@ -15,6 +15,11 @@ The norm's sum of squares is taken in a fixed order that depends on the tensors'
 (gym-usv_amd/csrc/usv_optim_math.hpp; tests/optim_ref.py restates it), so a run's parameters are bitwise
 reproducible, whatever the grid or the stream.  All on the current stream, without a host sync.
 
+``DeviceAdam(..., capturable=True)`` is the form a HIP graph can replay (``torch.optim.Adam``'s ``capturable``): the
+step number and ``lr`` live in a small block of device memory, a one-thread launch at the head of every ``step()``
+moves the number on and derives the bias corrections from it on the device (``usv_adam_step_dev``), and no kernel
+argument depends on the step.  ``gym_usv_amd.capture_step`` records such a step once and replays it.
+
 Two deviations from torch.  ``.grad`` is not written back: the clipped gradient exists in the kernel's registers
 only (SB3 discards it at the next ``zero_grad``).  A parameter whose ``.grad`` is None at ``step()`` is a
 ``ValueError``: torch skips such a parameter and keeps a step count per parameter, this class keeps one count for
@@ -27,6 +32,13 @@ import math
 import torch
 
 from . import _lib
+
+
+def refuse_capture(who, remedy):
+    """``RuntimeError`` where the current stream is recording a graph: ``who`` passes a host counter to its kernels
+    as an argument, which a graph would freeze."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{who} while the stream is capturing a graph: {remedy}")
 
 
 def _check_hyper(lr, betas, eps, max_grad_norm):
@@ -50,9 +62,23 @@ class DeviceAdam:
     """Adam with an optional global-norm gradient clip over ``params`` (float32, contiguous, on one ROCm device;
     anything else is a ``ValueError``; there is no CPU fallback).  ``lr``, ``betas``, ``eps`` and ``max_grad_norm`` are
     attributes read at every ``step``.  The moments live in two flat buffers (``exp_avg``, ``exp_avg_sq``: each
-    parameter's segment padded to four floats)."""
+    parameter's segment padded to four floats).
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lib_path=None):
+    ``capturable=True``: ``step()`` is legal inside ``torch.cuda.graph`` and a replay is a step that counts.  The step
+    number and ``lr`` live in a 32-byte device block (``usv_adam_step_dev``, include/usv_hip.h); ``step()`` issues one
+    launch more than the default form, the one thread that advances the block.  ``opt.lr = x`` writes the block with
+    an ordinary stream-ordered write (a ``RuntimeError`` while capturing: the write would be recorded, not made);
+    reading ``opt.step_count`` copies the block's number to the host, **a host sync**: keep it out of the training
+    loop.  The betas, ``eps`` and ``max_grad_norm`` are baked into a captured graph.  So are the addresses of the
+    gradients, hence the rule torch's whole-network capture uses: put ``zero_grad(set_to_none=True)`` *inside* the
+    captured region, so that the captured backward allocates the gradients from the graph's private pool, at
+    addresses that every replay finds again.  The bias corrections are derived on the device, whose ``pow`` is not
+    the host's: they are within one float32 ulp of the default form's, and where they are equal so is every result.
+
+    In the default form ``step()`` under capture is a ``RuntimeError``: it would freeze the step number."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, lib_path=None,
+                 capturable=False):
         params = list(params)
         if not params:
             raise ValueError("params must be a non-empty list of tensors")
@@ -63,11 +89,16 @@ class DeviceAdam:
                 raise ValueError("every parameter must be on one device")
         if params[0].device.type != "cuda":
             raise ValueError("DeviceAdam runs on a ROCm GPU only (no CPU fallback)")
-        self.lr, self.betas, self.eps, mg = _check_hyper(lr, betas, eps, max_grad_norm)
+        lr, self.betas, self.eps, mg = _check_hyper(lr, betas, eps, max_grad_norm)
         self.max_grad_norm = None if max_grad_norm is None else mg
         self.device = params[0].device
         self.lib = _lib.load(lib_path)
-        self.params, self.step_count = params, 0
+        self.params, self.capturable = params, bool(capturable)
+        self._clock = None
+        if self.capturable:                                  # lr (f64), step (i64), step_size and bc2_sqrt (f32), pad
+            words = (int(self.lib.usv_adam_clock_bytes()) + 7) // 8
+            self._clock = torch.zeros(words, dtype=torch.int64, device=self.device)
+        self.lr, self.step_count = lr, 0
         n = len(params)
         self._n = n
         self._table = (_lib.UsvAdamTensor * n)(*(_lib.UsvAdamTensor(p.data_ptr(), None, p.numel()) for p in params))
@@ -81,6 +112,42 @@ class DeviceAdam:
             self._offsets.append(at)
             at += (p.numel() + 3) // 4 * 4
 
+    @property
+    def lr(self):
+        return self._lr
+
+    @lr.setter
+    def lr(self, value):
+        if self._clock is not None:                          # the default form's is checked by the step that reads it
+            value = _check_hyper(value, (0.0, 0.0), 0.0, None)[0]
+            refuse_capture("DeviceAdam.lr was set", "set it between replays, outside the captured region")
+            self._clock[0:1].view(torch.float64).fill_(value)
+        self._lr = value
+
+    @property
+    def step_count(self):
+        """The number of steps taken.  With ``capturable=True`` it is read from the device block: a host sync."""
+        return self._steps if self._clock is None else int(self._clock[1].item())
+
+    @step_count.setter
+    def step_count(self, value):
+        value = int(value)
+        if value < 0:
+            raise ValueError("step_count must be >= 0")
+        if self._clock is not None:
+            refuse_capture("DeviceAdam.step_count was set", "set it outside the captured region")
+            self._clock[1:2].fill_(value)
+        self._steps = value
+
+    def clock(self):
+        """``capturable=True``: ``(step, lr, step_size, bc2_sqrt)`` of the last step as the device block holds them (the
+        two scalars as float32 values); a host sync, for tests and checkpoints."""
+        if self._clock is None:
+            raise RuntimeError("clock() is for capturable=True: the default form keeps no device block")
+        host = self._clock.cpu()
+        f = host.view(torch.float32)
+        return int(host[1]), float(host.view(torch.float64)[0]), f[4].item(), f[5].item()
+
     def zero_grad(self, set_to_none=True):
         for p in self.params:
             if set_to_none or p.grad is None:
@@ -90,8 +157,9 @@ class DeviceAdam:
                 p.grad.zero_()
 
     def step(self):
-        """Two launches (one without ``max_grad_norm``) per 96 tensors on the current stream.  Returns the norm of all
-        gradients before clipping as a 0-dim device tensor, or None without ``max_grad_norm``."""
+        """Two launches (one without ``max_grad_norm``) per 96 tensors on the current stream, and with ``capturable=True``
+        one more for the whole list.  Returns the norm of all gradients before clipping as a 0-dim device tensor, or
+        None without ``max_grad_norm``."""
         tab, keep = self._table, None
         for i, p in enumerate(self.params):
             g = p.grad
@@ -104,12 +172,19 @@ class DeviceAdam:
                 keep = (keep or []) + [g]                    # alive until the launches are queued
             tab[i].param, tab[i].grad = p.data_ptr(), g.data_ptr()
         mg = self.max_grad_norm
+        if self._clock is None:
+            refuse_capture("DeviceAdam.step() of a default (capturable=False) optimizer was called",
+                           "its step number is a kernel argument that a graph would freeze; make it with capturable=True")
         norm = None if mg is None else torch.empty((), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.usv_adam_step(
-            tab, self._n, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self._state_floats, self.step_count + 1,
-            self.lr, self.betas[0], self.betas[1], self.eps, -1.0 if mg is None else mg, self._scratch.data_ptr(),
-            self._scratch_floats, None if norm is None else norm.data_ptr(), _lib.stream_ptr(self.device)), self.lib)
-        self.step_count += 1
+        tail = (self.betas[0], self.betas[1], self.eps, -1.0 if mg is None else mg, self._scratch.data_ptr(),
+                self._scratch_floats, None if norm is None else norm.data_ptr(), _lib.stream_ptr(self.device))
+        head = (tab, self._n, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self._state_floats)
+        if self._clock is None:
+            _lib.check(self.lib.usv_adam_step(*head, self._steps + 1, self._lr, *tail), self.lib)
+            self._steps += 1
+        else:
+            _lib.check(self.lib.usv_adam_step_dev(*head, self._clock.data_ptr(), self._clock.numel() * 8, *tail),
+                       self.lib)
         return norm
 
     def _segment(self, buf, i):
@@ -121,10 +196,10 @@ class DeviceAdam:
         before the first step, as torch's) and one param group.  ``max_grad_norm`` is not part of it."""
         proto = torch.optim.Adam([torch.zeros(1)], lr=self.lr, betas=self.betas, eps=self.eps)
         group = dict(proto.param_groups[0], params=list(range(self._n)))
-        state = {}
-        if self.step_count > 0:
+        state, steps = {}, self.step_count
+        if steps > 0:
             for i in range(self._n):
-                state[i] = {"step": torch.tensor(float(self.step_count)),
+                state[i] = {"step": torch.tensor(float(steps)),
                             "exp_avg": self._segment(self.exp_avg, i).clone(),
                             "exp_avg_sq": self._segment(self.exp_avg_sq, i).clone()}
         return {"state": state, "param_groups": [group]}
@@ -154,5 +229,5 @@ class DeviceAdam:
             if k in state:
                 self._segment(self.exp_avg, i).copy_(state[k]["exp_avg"])
                 self._segment(self.exp_avg_sq, i).copy_(state[k]["exp_avg_sq"])
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.step_count = steps.pop() if steps else 0
+        self.betas, self.eps = betas, eps
+        self.lr, self.step_count = lr, steps.pop() if steps else 0          # capturable: both write the device block

@@ -226,7 +226,7 @@ class DevicePolyak:
     tau * p`` with three float32 roundings (the two-op ``t.mul_(1 - tau).add_(p, alpha=tau)`` without a fused
     multiply-add).  The tensors are float32, contiguous, on one ROCm device and pairwise of equal shape
     (``ValueError`` otherwise); zero-element tensors are skipped.  The device table of the pairs is built by the
-    first ``step`` and again whenever a ``data_ptr()`` has changed."""
+    first ``step`` (or by ``prepare()``) and again whenever a ``data_ptr()`` has changed."""
 
     def __init__(self, params, target_params, lib_path=None):
         src, dst = list(params), list(target_params)         # the tensors themselves: a rebound .data is seen
@@ -247,17 +247,41 @@ class DevicePolyak:
     def _current(self):
         return tuple(x.data_ptr() for x in self._src) + tuple(x.data_ptr() for x in self._dst)
 
+    def _pending(self):
+        """The current addresses, and whether the device table has to be built from them; (re)makes the host pairs and
+        the table's memory where it has."""
+        ptrs = self._current()
+        if ptrs == self._ptrs:
+            return ptrs, False
+        n = len(self._src)
+        self._pairs = (_lib.UsvPolyakPair * n)(*(_lib.UsvPolyakPair(p.data_ptr(), t.data_ptr(), p.numel())
+                                                 for p, t in zip(self._src, self._dst)))
+        nbytes = self.lib.usv_polyak_table_bytes(self._pairs, n)
+        self._table = torch.zeros(max(1, (nbytes + 7) // 8), dtype=torch.int64, device=self.device)
+        self._ptrs = None
+        return ptrs, True
+
+    def prepare(self):
+        """Uploads the device table now, where it is not up to date (a device synchronise and a host copy; nothing is
+        launched).  Call it before ``step`` is captured into a graph: an upload cannot be recorded."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("DevicePolyak.prepare() synchronises the device: call it before the capture begins")
+        ptrs, upload = self._pending()
+        if upload:
+            _lib.check(self.lib.usv_polyak_prepare(self._pairs, len(self._src), self._table.data_ptr(),
+                                                   self._table.numel() * 8), self.lib)
+            self._ptrs = ptrs
+
     def step(self, tau):
-        """One launch on the current stream."""
-        ptrs, upload = self._current(), 0
-        if ptrs != self._ptrs:
-            n = len(self._src)
-            self._pairs = (_lib.UsvPolyakPair * n)(*(_lib.UsvPolyakPair(p.data_ptr(), t.data_ptr(), p.numel())
-                                                     for p, t in zip(self._src, self._dst)))
-            nbytes = self.lib.usv_polyak_table_bytes(self._pairs, n)
-            self._table = torch.zeros(max(1, (nbytes + 7) // 8), dtype=torch.int64, device=self.device)
-            self._ptrs, upload = None, 1
+        """One launch on the current stream.  Legal inside ``torch.cuda.graph`` once the table is uploaded
+        (``prepare()``, or an earlier ``step``): with an upload pending while the stream is capturing it raises
+        ``RuntimeError``.  A captured step holds the table's address: the tensors must keep theirs."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing and self._current() != self._ptrs:
+            raise RuntimeError("DevicePolyak.step(): the table upload is pending (a first step, or a tensor has moved) "
+                               "while the stream is capturing a graph; call prepare() before the capture begins")
+        ptrs, upload = self._pending()
         _lib.check(self.lib.usv_polyak_update(self._pairs, len(self._src), self._table.data_ptr(), self._table.numel() * 8,
-                                              upload, ctypes.c_double(float(tau)), _lib.stream_ptr(self.device)),
+                                              int(upload), ctypes.c_double(float(tau)), _lib.stream_ptr(self.device)),
                    self.lib)
         self._ptrs = ptrs

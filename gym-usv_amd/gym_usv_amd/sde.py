@@ -38,6 +38,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import ptr as _ptr
+from .optim import refuse_capture
 
 MAX_LATENT = 4096
 
@@ -64,7 +65,7 @@ class _Squashed(torch.autograd.Function):
         n, A = head.n, head.act_dim
         act, env, gauss, var, logp = _fresh(head, (n, A), (n, A), (n, A), (n, A), (n,))
         head._squash_forward(mean, latent, std, (act, env, logp, gauss, var))
-        ctx.head, ctx.epoch = head, head._epoch
+        ctx.head, ctx.epoch, ctx.generation = head, head._epoch, head._generation
         ctx.save_for_backward(mean, latent, std, gauss, var)
         ctx.mark_non_differentiable(env, gauss)
         ctx.set_materialize_grads(False)                    # an unused output's gradient stays None: NULL, zeros
@@ -77,6 +78,10 @@ class _Squashed(torch.autograd.Function):
         mean, latent, std, gauss, var = ctx.saved_tensors
         n, L, A = head.n, head.latent_dim, head.act_dim
         g_act, g_logp = _contiguous(g_act, g_logp)
+        if head.capturable and head._generation != ctx.generation:
+            raise RuntimeError("DeviceSDE(capturable=True): the noise epoch was changed (reset_noise() or .epoch) between "
+                               "squashed() and its backward(), which reads the same device word: the backward would "
+                               "rebuild another matrix than the forward used")
         g_mean, g_lat, g_std = _fresh(head, (n, A), (n, L), (L, A))
         head._squash_backward(ctx.epoch, mean, latent, std, gauss, var, g_act, g_logp, g_mean, g_lat, g_std)
         need = ctx.needs_input_grad
@@ -129,10 +134,20 @@ class DeviceSDE:
 
     ``copy=False`` (default): ``sample`` returns this object's persistent buffers, overwritten by the next
     ``sample`` (stream-ordered: consume them on the same stream first, as ``DeviceRollout.put_obs`` and
-    ``env.step`` do).  ``copy=True`` returns fresh tensors.  There is no CPU fallback."""
+    ``env.step`` do).  ``copy=True`` returns fresh tensors.  There is no CPU fallback.
+
+    ``capturable=True``: the epoch is a word in device memory that the kernels read (the ``usv_sde_*_dev`` entries),
+    so ``sample``, ``weights`` and ``squashed`` with its backward are legal inside ``torch.cuda.graph`` and a replay
+    draws the noise of the epoch the word then holds.  ``reset_noise()`` is one launch of one thread
+    (``usv_counter_add``), to be captured with the rest; setting ``epoch`` is a stream-ordered write and reading it is
+    **a host sync**.  The backward of ``squashed`` reads the same word as its forward: a ``reset_noise()`` or an
+    ``epoch`` assignment between the two is an error, which eager code meets as a ``RuntimeError`` from
+    ``backward()`` (a host-side count of the changes; a replayed graph runs no host code and cannot be checked).
+    In the default form the four calls raise ``RuntimeError`` while the stream is capturing: the epoch is a kernel
+    argument there, and a graph would freeze it."""
 
     def __init__(self, num_envs, latent_dim, act_dim, device, seed, low, high, env_id_offset=0, copy=False,
-                 lib_path=None):
+                 lib_path=None, capturable=False):
         n, L, A = int(num_envs), int(latent_dim), int(act_dim)
         if n <= 0:
             raise ValueError("num_envs must be > 0")
@@ -153,7 +168,9 @@ class DeviceSDE:
         self.device, self.seed, self.env_id_offset, self.copy = device, seed, gid0, bool(copy)
         self.low = torch.tensor(lo, dtype=torch.float32, device=device)
         self.high = torch.tensor(hi, dtype=torch.float32, device=device)
-        self._epoch = 0
+        self.capturable = bool(capturable)
+        self._epoch, self._generation = 0, 0               # the host's epoch; how often the epoch has been changed
+        self._word = torch.zeros(1, dtype=torch.int32, device=device) if self.capturable else None
         self._s = _lib.UsvSde(n, L, A, 0, seed, gid0, (ctypes.c_float * 4)(*lo), (ctypes.c_float * 4)(*hi))
         self._sp = ctypes.byref(self._s)
         self._out = _fresh(self, (n, A), (n, A), (n,), make=torch.zeros)
@@ -162,16 +179,33 @@ class DeviceSDE:
 
     @property
     def epoch(self):
-        return self._epoch
+        return self._epoch if self._word is None else _lib.word_read(self._word)
 
     @epoch.setter
     def epoch(self, v):
-        self._epoch = int(v) & 0xFFFFFFFF
+        self._generation += 1
+        if self._word is None:
+            self._epoch = int(v) & 0xFFFFFFFF
+        else:
+            refuse_capture("DeviceSDE.epoch was set", "set it outside the captured region")
+            _lib.word_write(self._word, v)
 
     def reset_noise(self):
         """SB3's ``reset_noise`` / ``sample_weights``: a new matrix for every env from the next ``sample``
-        on.  A host integer; nothing runs on the device."""
-        self.epoch = self._epoch + 1
+        on.  A host integer, nothing runs on the device; with ``capturable=True`` one launch of one thread."""
+        if self._word is None:
+            self.epoch = self._epoch + 1
+        else:
+            self._generation += 1
+            _lib.check(self.lib.usv_counter_add(_ptr(self._word), 1, _lib.stream_ptr(self.device)), self.lib)
+
+    def _noise_entry(self, name, who):
+        """The C entry ``name`` and its epoch argument: the host integer, or ``name_dev`` and the device word."""
+        if self._word is not None:
+            return getattr(self.lib, name + "_dev"), _ptr(self._word)
+        refuse_capture(f"DeviceSDE.{who}() of a default (capturable=False) head was called",
+                       "its noise epoch is a kernel argument that a graph would freeze; make it with capturable=True")
+        return getattr(self.lib, name), self._epoch
 
     def sample(self, mean, latent, std, out=None):
         """``(a, a_env, logp)`` in one launch: ``a = mean + latent @ W`` [N, A] (unclipped, the rollout
@@ -189,7 +223,8 @@ class DeviceSDE:
         else:
             self._check(*zip(("out[0]", "out[1]", "out[2]"), out, ((n, A), (n, A), (n,))))
         a, a_env, logp = out
-        _lib.check(self.lib.usv_sde_sample(self._sp, self._epoch, _ptr(mean), _ptr(latent), stride, _ptr(std), _ptr(a),
+        fn, epoch = self._noise_entry("usv_sde_sample", "sample")
+        _lib.check(fn(self._sp, epoch, _ptr(mean), _ptr(latent), stride, _ptr(std), _ptr(a),
                                            _ptr(a_env), _ptr(logp), _lib.stream_ptr(self.device)), self.lib)
         if self.copy and out is self._out:
             return a.clone(), a_env.clone(), logp.clone()
@@ -204,8 +239,8 @@ class DeviceSDE:
             out, = _fresh(self, (n, L, A))
         else:
             self._check(("out", out, (n, L, A)))
-        _lib.check(self.lib.usv_sde_weights(self._sp, self._epoch, _ptr(std), _ptr(out),
-                                            _lib.stream_ptr(self.device)), self.lib)
+        fn, epoch = self._noise_entry("usv_sde_weights", "weights")
+        _lib.check(fn(self._sp, epoch, _ptr(std), _ptr(out), _lib.stream_ptr(self.device)), self.lib)
         return out
 
     def _check(self, *table):
@@ -230,17 +265,19 @@ class DeviceSDE:
         self._check(("mean", mean, (n, A)), ("std", std, (L, A)))
         stride = self._latent_stride("latent", latent)
         act, env, logp, gauss, var = out
-        _lib.check(self.lib.usv_sde_squash_forward(self._sp, self._epoch, _ptr(mean), _ptr(latent), stride, _ptr(std),
-                                                   _ptr(act), _ptr(env), _ptr(logp), _ptr(gauss), _ptr(var),
-                                                   _lib.stream_ptr(self.device)), self.lib)
+        fn, epoch = self._noise_entry("usv_sde_squash_forward", "squashed")
+        _lib.check(fn(self._sp, epoch, _ptr(mean), _ptr(latent), stride, _ptr(std), _ptr(act), _ptr(env), _ptr(logp),
+                      _ptr(gauss), _ptr(var), _lib.stream_ptr(self.device)), self.lib)
 
     def _squash_backward(self, epoch, mean, latent, std, gauss, var, g_act, g_logp, g_mean, g_lat, g_std):
         n, L, A = self.n, self.latent_dim, self.act_dim
         self._check(("g_act", g_act, (n, A)), ("g_logp", g_logp, (n,)), ("g_mean", g_mean, (n, A)),
                     ("g_std", g_std, (L, A)), ("gauss", gauss, (n, A)), ("var", var, (n, A)))
         scratch = self._grown("_scratch", self.lib.usv_sde_squash_scratch_floats(self._sp))
-        _lib.check(self.lib.usv_sde_squash_backward(
-            self._sp, epoch, _ptr(mean), _ptr(latent), self._latent_stride("latent", latent), _ptr(std), _ptr(gauss),
+        fn, word = self._noise_entry("usv_sde_squash_backward", "squashed")
+        _lib.check(fn(
+            self._sp, epoch if self._word is None else word, _ptr(mean), _ptr(latent),
+            self._latent_stride("latent", latent), _ptr(std), _ptr(gauss),
             _ptr(var), _ptr(g_act), _ptr(g_logp), _ptr(g_mean), _ptr(g_lat), self._latent_stride("g_lat", g_lat),
             _ptr(g_std), _ptr(scratch), _lib.stream_ptr(self.device)), self.lib)
 
@@ -258,7 +295,8 @@ class DeviceSDE:
         gradients of ``actions`` and ``log_prob`` with respect to ``mean``, ``latent`` (through the noise and
         the variance) and ``std`` (chain ``log_std.exp()`` in front and autograd carries it into ``log_std``).
         ``env_actions`` and ``gaussian_actions`` carry no gradient.  The epoch is the forward's: a
-        ``reset_noise()`` before ``backward()`` does not change the backward's matrix.  The backward's scratch
+        ``reset_noise()`` before ``backward()`` does not change the backward's matrix (with ``capturable=True`` it is
+        an error: see the class).  The backward's scratch
         belongs to the head: backward calls of one head must be stream-ordered.
 
         How SAC uses it.  One head of ``num_envs`` rows collects: rows are global env ids, and

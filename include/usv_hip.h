@@ -889,6 +889,57 @@ int usv_ppo_loss(int32_t rows, const float* logp, const float* old_logp, const f
 int usv_ppo_explained_variance(int32_t rows, const float* values, const float* returns, float* out /* 1 float */,
                                float* scratch, void* stream);
 
+/* ---- Graph-capturable update: the step and noise counters of the entries above in device memory (ABI v5
+ * additions).  A captured HIP graph freezes kernel arguments, so a replay of usv_adam_step would repeat the bias
+ * correction of the captured step and a replay of a noise entry would redraw the captured epoch's noise.  These forms
+ * read the counters from device words that kernels inside the graph advance.  Handle-free and stream-ordered; every
+ * existing entry, its kernel and its results are unchanged.  No entry here allocates, synchronises or copies from the
+ * host: all are legal while `stream` is capturing, and the device-memory checks of the buffers stay on (the runtime
+ * answers hipPointerGetAttributes during a capture).
+ *
+ * usv_counter_add: word_dev[0] += inc, wrapping at 2^32 as a host uint32 epoch does; one launch of one thread.
+ *
+ * usv_sde_sample_dev / usv_sde_weights_dev / usv_sde_squash_forward_dev / usv_sde_squash_backward_dev /
+ * usv_caps_perturb_dev: the entry without _dev, with the epoch read from epoch_dev[0] by the kernel (once per wave)
+ * where the other takes `epoch` as an argument.  Same kernel body, bit-equal results for an equal epoch.  A backward
+ * reads the word when it runs: the word must not change between a forward and its backward.
+ *
+ * usv_adam_step_dev: usv_adam_step with the step number and lr in the clock block clock_dev (usv_adam_clock_bytes()
+ * bytes of device memory, 16-B aligned; clock_bytes is its size):
+ *     offset 0   double  lr                   the caller writes it (stream-ordered) and may change it between steps
+ *     offset 8   int64   step                 the number of the last step taken: 0 before the first
+ *     offset 16  float   step_size, bc2_sqrt  of that step, derived on the device
+ * One launch of one thread, ahead of the call's other launches, sets step += 1 and derives step_size = lr / (1 -
+ * beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) in double, each cast once to f32 (adam_clock_scalars,
+ * gym-usv_amd/csrc/usv_optim_math.hpp): once per call however many launches the list takes, so one launch more than
+ * usv_adam_step.  The device's pow is not the host's: the two scalars are within 1 f32 ulp of usv_adam_step's, and where
+ * they are equal so is every result.  The betas, eps and max_grad_norm stay arguments.
+ *
+ * usv_polyak_prepare: usv_polyak_update's table upload alone (it synchronises; nothing is launched).  While `stream` is
+ * capturing, usv_polyak_update with upload != 0 is refused with USV_ERR_ARG before it synchronises: prepare first.
+ *
+ * Refused with USV_ERR_ARG before any HIP call: a NULL or not 4-B aligned word_dev or epoch_dev, a NULL or not 16-B
+ * aligned clock_dev, clock_bytes below usv_adam_clock_bytes(), and what the entry without _dev refuses. */
+int usv_counter_add(uint32_t* word_dev, uint32_t inc, void* stream);
+int usv_sde_sample_dev(const usv_sde* s, const uint32_t* epoch_dev, const float* mean, const float* lat, size_t stride,
+                       const float* std, float* act, float* act_env, float* logp, void* stream);
+int usv_sde_weights_dev(const usv_sde* s, const uint32_t* epoch_dev, const float* std, float* w, void* stream);
+int usv_sde_squash_forward_dev(const usv_sde* s, const uint32_t* epoch_dev, const float* mean, const float* lat,
+                               size_t stride, const float* std, float* act, float* act_env, float* logp, float* gauss,
+                               float* var, void* stream);
+int usv_sde_squash_backward_dev(const usv_sde* s, const uint32_t* epoch_dev, const float* mean, const float* lat,
+                                size_t stride, const float* std, const float* gauss, const float* var,
+                                const float* g_act, const float* g_logp, float* g_mean, float* g_lat, size_t g_stride,
+                                float* g_std, float* scratch, void* stream);
+int usv_caps_perturb_dev(int32_t rows, int32_t width, const float* obs, float* out, float eps, uint64_t seed,
+                         const uint32_t* epoch_dev, void* stream);
+size_t usv_adam_clock_bytes(void);
+int usv_adam_step_dev(const usv_adam_tensor* tensors_host, int32_t n, float* m, float* v, size_t state_floats,
+                      void* clock_dev, size_t clock_bytes, double beta1, double beta2, double eps,
+                      double max_grad_norm /* < 0: none */, float* scratch, size_t scratch_floats, float* norm_out,
+                      void* stream);
+int usv_polyak_prepare(const usv_polyak_pair* pairs_host, int32_t n_pairs, void* table_dev, size_t table_bytes);
+
 /* Select the step-kernel variant of a usv-simple / usv-asmc-simple handle (verification and
  * tuning: every variant computes bit-identical outputs, tests/test_gpu_*.py compare them bitwise).
  * No reference counterpart; usv_create picks the tuned default.
