@@ -55,6 +55,20 @@ this image, so this is a compact PPO with the same hyper-parameters where they c
   (one call per update on the rollout's values and returns), read back with the other statistics once per update.
   ``--check-loss`` (a test mode) also evaluates the torch lines on every minibatch and records ``loss_diff``, the
   largest difference of each of the three losses over the sum of the magnitudes of its terms.
+* ``--perm-kernel`` (with ``--fused``, with or without ``--frames``; ``train(fused=True, perm_kernel=True)``): the
+  update draws its minibatches from ``DeviceRollout.sampler``: one C call per minibatch in place of ``randperm`` and
+  ``gather`` (or fancy indexing), no index tensor.  The order is a keyed bijection of the rollout's samples that the
+  gather kernel computes itself, with a device cursor that the call advances; every epoch still visits every sample
+  once.  ``batch_size`` must divide ``envs * n_steps``.  The order differs from ``randperm``'s, so runs with and
+  without the flag are two samples of the same algorithm.
+* ``--graph`` (``train(..., graph=True)``; needs ``--fused --sde-kernel --eval-kernel --adam-kernel --loss-kernel
+  --perm-kernel``, refuses ``--check-eval`` and ``--check-loss``): one minibatch step -- ``sampler.next`` into static
+  tensors, the forward, ``DevicePPOLoss.loss``, ``zero_grad``, the backward, ``DeviceAdam(capturable=True).step()``
+  and the statistics' running sum -- is recorded once as a HIP graph (``gym_usv_amd.capture_step``) and an update is
+  ``n_epochs * envs * n_steps / batch_size`` replays with nothing launched in between.  The warm-up and capture
+  calls train on the first minibatches: parameters, optimizer state and the sampler's cursor are put back behind
+  them, so the run takes exactly the gradient steps of the run without ``--graph``.  ``clip``, ``vf_coef``,
+  ``ent_coef`` and ``clip_range_vf`` are kernel arguments and frozen in the graph.
 * ``--clip-range-vf X`` (SB3's ``clip_range_vf``, default none) and ``--no-normalize-advantage`` (SB3's
   ``normalize_advantage=False``) apply with and without ``--loss-kernel``.
 
@@ -137,7 +151,8 @@ class PPO:
     """Rollout + update over a ``UsvVectorEnv`` (any registered id with a Box action space)."""
 
     def __init__(self, env, n_steps=32, batch_size=4096, seed=0, fused=False, frames=False, sde_kernel=False,
-                 eval_kernel=False, check_eval=False, adam_kernel=False, loss_kernel=False, check_loss=False, **cfg):
+                 eval_kernel=False, check_eval=False, adam_kernel=False, loss_kernel=False, check_loss=False,
+                 perm_kernel=False, graph=False, **cfg):
         from gym_usv_amd.sb3 import DeviceFrameStack
         self.cfg = dict(CONFIG_PPO, **cfg)
         self.env, self.n_steps, self.batch_size = env, n_steps, batch_size
@@ -148,6 +163,10 @@ class PPO:
         if frames and not fused:
             raise ValueError("frames=True needs fused=True")
         self.frames = frames
+        check_graph_args(graph, fused, sde_kernel, eval_kernel, adam_kernel, loss_kernel, perm_kernel, check_eval, check_loss)
+        if perm_kernel and not fused:
+            raise ValueError("perm_kernel=True needs fused=True: the sampler reads a DeviceRollout")
+        self.perm_kernel, self.graph, self.captured, self.sampler = perm_kernel, graph, None, None
         if sde_kernel and not (fused and self.cfg["use_sde"]):
             raise ValueError("sde_kernel=True needs fused=True and use_sde=True")
         if (eval_kernel or check_eval) and not (fused and sde_kernel):
@@ -171,7 +190,8 @@ class PPO:
         self.adam_kernel = adam_kernel
         if adam_kernel:
             from gym_usv_amd import DeviceAdam
-            self.opt = DeviceAdam(self.model.parameters(), lr=self.cfg["lr"], max_grad_norm=self.cfg["max_grad_norm"])
+            self.opt = DeviceAdam(self.model.parameters(), lr=self.cfg["lr"], max_grad_norm=self.cfg["max_grad_norm"],
+                                  capturable=graph)          # the step number in device memory: a replayed step counts
         else:
             self.opt = torch.optim.Adam(self.model.parameters(), lr=self.cfg["lr"])
         lo, hi = env.single_action_space.low, env.single_action_space.high
@@ -189,6 +209,8 @@ class PPO:
             self.ro = DeviceRollout(self.N, n_steps, k * D, A, self.device, env.reward.dtype,
                                     n_stack=k if frames else None)
             self.wr.reset(obs)
+            if perm_kernel:                             # a key of its own, as the head's below
+                self.sampler = self.ro.sampler(batch_size, seed ^ 0x9E3779B97F4A7C15)
             if sde_kernel:
                 from gym_usv_amd import DeviceSDE
                 # a key of its own: the env's resets draw from the same generator keyed by `seed`
@@ -339,8 +361,8 @@ class PPO:
                 self._eval_diff = worst if self._eval_diff is None else torch.maximum(self._eval_diff, worst)
         return logp, pg, None
 
-    def update_record(self, stats):
-        s = torch.stack(stats).mean(0)
+    def update_record(self, s):
+        """The update's record from ``s``, the mean of its minibatches' statistics."""
         if self.loss_kernel:                            # one read for the update's means and explained_variance
             s = torch.cat((s, self._ev.reshape(1)))
         s = s.tolist()
@@ -424,6 +446,8 @@ class PPO:
         M = self.n_steps * self.N
         if self.loss_kernel:
             self._ev = self.ppo_loss.explained_variance(self.b_val, ret)
+        if self.perm_kernel:
+            return self.update_perm()
         if self.frames:
             return self.update_frames(M)
         obs = self.b_obs.reshape(M, -1)
@@ -437,7 +461,7 @@ class PPO:
                 loss, stat = self.minibatch_loss(obs[i], act[i], logp0[i], adv[i], ret[i], val0[i])
                 self.gradient_step(loss)
                 stats.append(stat)
-        return self.update_record(stats)
+        return self.update_record(torch.stack(stats).mean(0))
 
     def update_frames(self, M):
         """``update``'s loop with every minibatch read by ``DeviceRollout.gather`` (frame storage has no
@@ -452,7 +476,54 @@ class PPO:
                                                  mb.old_values)
                 self.gradient_step(loss)
                 stats.append(stat)
-        return self.update_record(stats)
+        return self.update_record(torch.stack(stats).mean(0))
+
+    def update_perm(self):
+        """``update``'s loop on ``DeviceRollout.sampler``: no permutation tensor, one C call per minibatch; with
+        ``graph`` the whole minibatch step is a replay."""
+        steps = self.cfg["n_epochs"] * self.sampler.batches_per_epoch
+        if self.graph:
+            if self.captured is None:
+                self.capture()
+            self.acc.zero_()
+            for _ in range(steps):
+                self.captured.replay()                  # nothing else is launched in between
+            return self.update_record(self.acc / steps)
+        stats = []
+        for _ in range(steps):
+            stats.append(self.sampled_step(None))
+        return self.update_record(torch.stack(stats).mean(0))
+
+    def sampled_step(self, out):
+        """One minibatch step behind ``sampler.next`` (into ``out``, or fresh tensors); returns its statistics."""
+        mb = self.sampler.next(out=out)
+        loss, stat = self.minibatch_loss(mb.observations, mb.actions, mb.old_log_prob, mb.advantages, mb.returns,
+                                         mb.old_values)
+        self.gradient_step(loss)
+        return stat
+
+    def graph_step(self):
+        self.acc += self.sampled_step(self.static_mb)
+        return self.acc
+
+    def capture(self):
+        """Records ``graph_step``.  The warm-up and capture calls train on the update's first minibatches: what they
+        changed (parameters, optimizer state, the sampler's cursor) is put back, so the first replay is the run's
+        first gradient step."""
+        from gym_usv_amd import RolloutSamples, capture_step
+        B, W, A = self.batch_size, self.ro.w, self.ro.a
+        z = lambda *shape: torch.zeros(shape, device=self.device)   # noqa: E731
+        self.static_mb = RolloutSamples(z(B, W), z(B, A), z(B), z(B), z(B), z(B))
+        self.acc = z(5)
+        nets = list(self.model.parameters())
+        kept = [p.detach().clone() for p in nets]
+        opt_state, cursor = self.opt.state_dict(), self.sampler.state_dict()
+        self.captured = capture_step(self.graph_step)
+        with torch.no_grad():
+            for p, k in zip(nets, kept):
+                p.copy_(k)                              # in place: the graph holds the addresses
+        self.opt.load_state_dict(opt_state)
+        self.sampler.load_state_dict(cursor)
 
     def episode_stats(self):
         out = {"mean_abs_ye": float(torch.stack(self.abs_ye).mean())} if self.abs_ye else {}
@@ -473,16 +544,37 @@ class PPO:
                 "ep_len_mean": float(f[:, 1].mean()), **out}
 
 
+def check_graph_args(graph, fused, sde_kernel, eval_kernel, adam_kernel, loss_kernel, perm_kernel, check_eval, check_loss):
+    if not graph:
+        return
+    missing = [name for name, on in (("--fused", fused), ("--sde-kernel", sde_kernel), ("--eval-kernel", eval_kernel),
+                                     ("--adam-kernel", adam_kernel), ("--loss-kernel", loss_kernel),
+                                     ("--perm-kernel", perm_kernel)) if not on]
+    if missing:
+        raise ValueError("--graph records the minibatch step of the HIP kernels: it also needs " + " ".join(missing) +
+                         " (a step with torch's own head, loss, optimizer or permutation is not recorded)")
+    if check_eval or check_loss:
+        raise ValueError("--graph does not go with --check-eval or --check-loss: the test modes run outside a graph")
+
+
 def train(env_id="usv-simple", envs=4096, updates=10, n_steps=32, batch_size=4096, seed=0, log=print, fused=False,
           frames=False, sde_kernel=False, eval_kernel=False, check_eval=False, adam_kernel=False, loss_kernel=False,
-          check_loss=False, **cfg):
+          check_loss=False, perm_kernel=False, graph=False, keep=None, **cfg):
+    """``keep``: a dict that receives the ``PPO`` object under "ppo" (tests read its parameters and counters)."""
     import gym_usv_amd
     if check_loss and not loss_kernel:
         raise ValueError("check_loss compares the loss kernel with torch: it needs loss_kernel=True")
+    check_graph_args(graph, fused, sde_kernel, eval_kernel, adam_kernel, loss_kernel, perm_kernel, check_eval, check_loss)
+    if perm_kernel and not fused:
+        raise ValueError("perm_kernel=True needs fused=True: the sampler reads a DeviceRollout")
+    if perm_kernel and (int(envs) * int(n_steps)) % int(batch_size) != 0:
+        raise ValueError("perm_kernel=True needs a batch_size that divides envs * n_steps")
     env = gym_usv_amd.make_vec(env_id, envs, seed=seed, copy=False)   # each step is consumed at once
     ppo = PPO(env, n_steps=n_steps, batch_size=batch_size, seed=seed, fused=fused, frames=frames,
               sde_kernel=sde_kernel, eval_kernel=eval_kernel, check_eval=check_eval, adam_kernel=adam_kernel,
-              loss_kernel=loss_kernel, check_loss=check_loss, **cfg)
+              loss_kernel=loss_kernel, check_loss=check_loss, perm_kernel=perm_kernel, graph=graph, **cfg)
+    if keep is not None:
+        keep["ppo"] = ppo
     hist = []
     t0 = time.perf_counter()
     for u in range(updates):
@@ -520,6 +612,10 @@ def main():
                     help="the minibatch loss, approx_kl and clip_fraction through DevicePPOLoss; explained_variance per update")
     ap.add_argument("--check-loss", action="store_true",
                     help="with --loss-kernel: also evaluate the torch lines on every minibatch and record loss_diff")
+    ap.add_argument("--perm-kernel", action="store_true",
+                    help="with --fused: minibatches from DeviceRollout.sampler (an in-kernel permutation, a device cursor)")
+    ap.add_argument("--graph", action="store_true",
+                    help="record a minibatch step as a HIP graph and replay it (needs --fused and the five kernel flags)")
     ap.add_argument("--clip-range-vf", type=float, default=None, help="SB3's clip_range_vf (default: none)")
     ap.add_argument("--no-normalize-advantage", action="store_true", help="SB3's normalize_advantage=False")
     ap.add_argument("--log", default=None, help="also append the JSON lines to this file")
@@ -532,6 +628,15 @@ def main():
         ap.error("--eval-kernel and --check-eval need --sde-kernel")
     if a.check_loss and not a.loss_kernel:
         ap.error("--check-loss needs --loss-kernel")
+    if a.perm_kernel and not a.fused:
+        ap.error("--perm-kernel needs --fused")
+    if a.perm_kernel and (a.envs * a.n_steps) % a.batch_size != 0:
+        ap.error("--perm-kernel needs a --batch-size that divides --envs * --n-steps")
+    try:
+        check_graph_args(a.graph, a.fused, a.sde_kernel, a.eval_kernel, a.adam_kernel, a.loss_kernel, a.perm_kernel,
+                         a.check_eval, a.check_loss)
+    except ValueError as e:
+        ap.error(str(e))
     f = open(a.log, "a") if a.log else None
 
     def log(s):
@@ -545,11 +650,13 @@ def main():
                                    "fused": a.fused, "frames": a.frames, "sde_kernel": a.sde_kernel,
                                    "eval_kernel": a.eval_kernel, "check_eval": a.check_eval,
                                    "adam_kernel": a.adam_kernel, "loss_kernel": a.loss_kernel,
-                                   "check_loss": a.check_loss, "clip_range_vf": a.clip_range_vf,
+                                   "check_loss": a.check_loss, "perm_kernel": a.perm_kernel, "graph": a.graph,
+                                   "clip_range_vf": a.clip_range_vf,
                                    "normalize_advantage": not a.no_normalize_advantage}}))
     train(a.env_id, a.envs, a.updates, a.n_steps, a.batch_size, a.seed, log=log, fused=a.fused, frames=a.frames,
           sde_kernel=a.sde_kernel, eval_kernel=a.eval_kernel, check_eval=a.check_eval, adam_kernel=a.adam_kernel,
-          loss_kernel=a.loss_kernel, check_loss=a.check_loss, use_sde=not a.no_sde, clip_range_vf=a.clip_range_vf,
+          loss_kernel=a.loss_kernel, check_loss=a.check_loss, perm_kernel=a.perm_kernel, graph=a.graph,
+          use_sde=not a.no_sde, clip_range_vf=a.clip_range_vf,
           normalize_advantage=not a.no_normalize_advantage)
 
 

@@ -48,6 +48,11 @@
 //                         (host C++, no HIP)
 //   usv_ppo.hpp           PPO loss: two moment kernels and the fused loss on usv_sac.hpp's reduction
 //                         (usv_ppo_loss / usv_ppo_explained_variance)
+//   usv_rollout_gather.inc  the minibatch gather, stated once and included twice: by usv_rollout_frames.hpp with the
+//                         indices in a tensor, by usv_rollout_perm.hpp with a cursor and a keyed permutation
+//   usv_rollout_perm_math.hpp  the permutation (Feistel network, cycle walking, Philox keys) and the minibatch cursor
+//                         (host C++, no HIP)
+//   usv_rollout_perm.hpp  the gather a graph can replay and the cursor's tick (usv_rollout_gather_perm)
 // Reference: see include/usv_hip.h for the file:line each entry point replaces.
 #include <hip/hip_runtime.h>
 
@@ -80,7 +85,8 @@
 #include "usv_sac.hpp"           // (after the others: every kernel before it keeps its place in the code object)
 #include "usv_caps.hpp"          // (after usv_sac.hpp, for the same reason)
 #include "usv_optim.hpp"         // (after usv_caps.hpp, for the same reason)
-#include "usv_ppo.hpp"           // (last, for the same reason)
+#include "usv_ppo.hpp"           // (after usv_optim.hpp, for the same reason)
+#include "usv_rollout_perm.hpp"  // (last, for the same reason)
 
 // ============================================================================= host side
 using namespace usv;
@@ -1287,6 +1293,51 @@ int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, cons
   const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
   hipLaunchKernelGGL(rollout_gather_kernel, grid, block, 0, (hipStream_t)stream, a, f, idx, (int)B, obs_out, act_out,
                      val_out, logp_out, adv_out, ret_out);
+  HIP_TRY(hipGetLastError());
+  return USV_OK;
+}
+
+// ---- the gather a graph can replay (usv_rollout_perm.hpp)
+size_t usv_rollout_cursor_bytes(void) { return sizeof(RolloutCursor); }
+
+int usv_rollout_gather_perm(const usv_rollout* ro, const usv_rollout_frames* fr, void* cursor_dev, uint64_t seed,
+                            int32_t B, int64_t* idx_out, float* obs_out, float* act_out, float* val_out,
+                            float* logp_out, float* adv_out, float* ret_out, void* stream) {
+  RoArgs a;
+  int dev;
+  const char* const fn = "usv_rollout_gather_perm";
+  if (int rc = rollout_frames_check(ro, fr)) return rc;
+  if (B <= 0) return fail(USV_ERR_ARG, "usv_rollout_gather_perm: B must be > 0");
+  if (!fr->bad_count) return fail(USV_ERR_ARG, "usv_rollout_gather_perm: null bad_count");
+  if (!cursor_dev) return fail(USV_ERR_ARG, "usv_rollout_gather_perm: null cursor block");
+  if ((reinterpret_cast<uintptr_t>(cursor_dev) & 15) != 0)
+    return fail(USV_ERR_ARG, "usv_rollout_gather_perm: the cursor block is not 16-B aligned");
+  const Bufs more = {{cursor_dev, 16}, {fr->bad_count, 4}, {obs_out, 4},  {act_out, 4},      {val_out, 4},
+                     {logp_out, 4},    {adv_out, 4},       {ret_out, 4},  {idx_out, 8, true}};
+  // refuse_gather_bufs's checks, with the cursor in the place of idx (it is not null) and idx_out as it may be null
+  if (int rc = refuse_gather_bufs(fn, (const int64_t*)cursor_dev, more.begin() + 2, 6)) return rc;
+  if ((reinterpret_cast<uintptr_t>(idx_out) & 7) != 0) return fail(USV_ERR_ARG, "usv_rollout_gather_perm: idx_out is not 8-B aligned");
+  for (const Buf* b = more.begin() + 2; b != more.end(); ++b)
+    if (b->p == cursor_dev) return fail(USV_ERR_ARG, "usv_rollout_gather_perm: an output aliases the cursor block");
+  if (ro->n > 0 && ro->n_steps > 0) {                   // (rollout_args refuses the rest)
+    const int64_t M = (int64_t)ro->n_steps * ro->n;
+    if (M % B != 0)
+      return fail(USV_ERR_ARG, "usv_rollout_gather_perm: B must divide n_steps * n (a recorded graph has one shape)");
+  }
+  usv_rollout r = *ro;
+  if (fr->frames) r.obs = fr->frames;
+  if (int rc = rollout_args(&r, true, more, a, dev)) return rc;
+  const int64_t batches = (int64_t)a.T * a.n / B;       // the cursor's batch word is a uint32
+  if (batches > 0xffffffffll) return fail(USV_ERR_ARG, "usv_rollout_gather_perm: more than 2^32 - 1 minibatches an epoch");
+  const uint32_t n_batches = (uint32_t)batches;
+  DeviceGuard g(dev);
+  const RfArgs f{fr->k, fr->d, fr->flags & USV_ROLLOUT_FRAMES_CLEAR_KEEPS_SIGN, fr->frames, fr->bad_count};
+  const int per_block = kWaves * kRfRows;
+  const dim3 grid((unsigned)(((int64_t)B + per_block - 1) / per_block)), block(kBlock);
+  RolloutCursor* const cur = (RolloutCursor*)cursor_dev;
+  hipLaunchKernelGGL(rollout_gather_perm_kernel, grid, block, 0, (hipStream_t)stream, a, f, (const RolloutCursor*)cur, seed,
+                     n_batches, idx_out, (int)B, obs_out, act_out, val_out, logp_out, adv_out, ret_out);
+  hipLaunchKernelGGL(rollout_cursor_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, cur, n_batches);
   HIP_TRY(hipGetLastError());
   return USV_OK;
 }

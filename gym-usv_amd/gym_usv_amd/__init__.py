@@ -14,7 +14,7 @@ The compute lives in libusvhip.so (HIP, gfx950) behind the C-ABI in include/usv_
 """
 from ._lib import UsvLibError, load as load_library  # noqa: F401
 from .vector_env import ENV_SPECS, UsvVectorEnv  # noqa: F401
-from .rollout import DeviceRollout  # noqa: F401
+from .rollout import DeviceRollout, RolloutSampler, RolloutSamples  # noqa: F401
 from .sde import DeviceSDE, Evaluation, SquashedSample  # noqa: F401
 from .replay import DeviceReplay, NStepReplaySamples, ReplaySamples  # noqa: F401
 from .sac import CriticLoss, DevicePolyak, DeviceSACLoss, PolicyLoss  # noqa: F401
@@ -26,7 +26,7 @@ from .graph import CapturedStep, capture_step  # noqa: F401
 __all__ = ["make", "make_vec", "make_sb3_vec_env", "registry", "UsvVectorEnv", "UsvLibError", "ENV_SPECS",
            "DeviceRollout", "DeviceSDE", "DeviceReplay", "ReplaySamples", "NStepReplaySamples",
            "DeviceSACLoss", "DevicePolyak", "CriticLoss", "PolicyLoss", "DeviceCAPS", "SmoothLoss", "DeviceAdam",
-           "DevicePPOLoss", "PPOLoss", "capture_step", "CapturedStep"]
+           "DevicePPOLoss", "PPOLoss", "capture_step", "CapturedStep", "RolloutSampler", "RolloutSamples"]
 
 registry = {k: {"entry_point": f"gym_usv_amd.envs:{cls}", "max_episode_steps": v[1] or None}
             for (k, v), cls in zip(ENV_SPECS.items(), ("UsvSimpleEnv", "UsvSimpleASMCEnv", "UsvAsmcEnv",

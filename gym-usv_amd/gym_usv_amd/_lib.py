@@ -228,6 +228,9 @@ SIGNATURES = [
     ("usv_adam_step_dev", ctypes.c_int, [ctypes.POINTER(UsvAdamTensor), _i32, _vp, _vp, _sz, _vp, _sz, ctypes.c_double,
                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _sz, _vp, _vp]),
     ("usv_polyak_prepare", ctypes.c_int, [ctypes.POINTER(UsvPolyakPair), _i32, _vp, _sz]),
+    ("usv_rollout_cursor_bytes", _sz, []),
+    ("usv_rollout_gather_perm", ctypes.c_int, [ctypes.POINTER(UsvRollout), ctypes.POINTER(UsvRolloutFrames), _vp, _u64,
+                                               _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
 
 _LIBS = {}

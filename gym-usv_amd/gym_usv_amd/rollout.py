@@ -26,6 +26,18 @@ The other half of ``RolloutBuffer``, ``get``, is one more kernel (``usv_rollout_
         mb.observations, mb.actions, mb.old_values, mb.old_log_prob, mb.advantages, mb.returns
     mb = ro.gather(idx)                                   # any int64 [B] of flat indices t * N + e
 
+``ro.sampler(batch_size, seed)`` is ``get`` without a stored permutation, in the form a HIP graph can replay
+(``usv_rollout_gather_perm``)::
+
+    smp = ro.sampler(4096, seed)                          # batch_size must divide T * N
+    for _ in range(n_epochs * smp.batches_per_epoch):
+        mb = smp.next()                                   # one C call; every epoch visits every sample once
+
+Which minibatch comes next is a two-word cursor in device memory that the call itself advances, and the sample of
+each position is a keyed bijection of [0, T * N) computed in the gather kernel from (seed, epoch, position)
+(gym-usv_amd/csrc/usv_rollout_perm_math.hpp; tests/rollout_perm_ref.py restates it): no ``randperm``, no index
+tensor, and no kernel argument that changes from one minibatch to the next.
+
 ``DeviceRollout(..., n_stack=k)`` keeps one ``D``-float frame per (step, env) in ``frames``
 [N, T + k - 1, D] where the default keeps the whole ``k * D`` stack in ``obs``; ``gather`` rebuilds the
 stacked rows, bit for bit the rows full storage would hold (tests/rollout_frames_ref.py).
@@ -210,15 +222,24 @@ class DeviceRollout:
         if idx.dtype != torch.int64 or not 0 < B < 2 ** 31 or idx.device != self.device:
             raise ValueError(f"idx must be a non-empty 1-D int64 tensor (below 2^31 indices) on {self.device}")
         idx = idx.contiguous()
-        shapes = ((B, self.w), (B, self.a), (B,), (B,), (B,), (B,))
-        if out is None:
-            out = RolloutSamples(*(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes))
-        else:
-            for name, t, s in zip(RolloutSamples._fields, out, shapes):
-                self._check(f"out.{name}", t, torch.float32, s)
+        out = self._out(B, out)
         _lib.check(self.lib.usv_rollout_gather(self._rp, self._fp, _ptr(idx), B, *(_ptr(t) for t in out),
                                                self._stream()), self.lib)
+        return out
+
+    def _out(self, B, out):
+        """``gather``'s outputs for ``B`` samples: fresh tensors, or those of ``out`` checked."""
+        shapes = ((B, self.w), (B, self.a), (B,), (B,), (B,), (B,))
+        if out is None:
+            return RolloutSamples(*(torch.empty(s, dtype=torch.float32, device=self.device) for s in shapes))
+        for name, t, s in zip(RolloutSamples._fields, out, shapes):
+            self._check(f"out.{name}", t, torch.float32, s)
         return out if isinstance(out, RolloutSamples) else RolloutSamples(*out)
+
+    def sampler(self, batch_size, seed=0):
+        """A ``RolloutSampler`` over this rollout: minibatches of ``batch_size`` (it must divide ``T * N``:
+        ``ValueError``) in the order that ``seed`` (a 64-bit integer) keys."""
+        return RolloutSampler(self, batch_size, seed)
 
     def get(self, batch_size, generator=None):
         """SB3's ``RolloutBuffer.get``: one ``torch.randperm(T * N)`` on the device (``generator``: a
@@ -236,3 +257,80 @@ class DeviceRollout:
         """How many indices ``gather`` has refused since this object was built, as a Python int (one
         host copy: a sync, like ``counts``)."""
         return int(self._bad.item())
+
+
+class RolloutSampler:
+    """SB3's ``RolloutBuffer.get`` as a sequence of ``next()`` calls that a HIP graph can replay.
+
+    Epoch ``e`` visits the samples in the order ``perm_index(seed, e, T * N, 0 .. T * N - 1)``, a keyed bijection
+    that the gather kernel evaluates itself; minibatch ``b`` of an epoch is positions ``b * batch_size ..``.  The
+    cursor ``(epoch, batch)`` lives in a 16-byte device block that every ``next()`` advances on the device, so a
+    recorded ``next()`` reads another minibatch at every replay, and ``n_epochs * batches_per_epoch`` calls are
+    ``n_epochs`` passes over the rollout.  The sampler reads the rollout as it is when ``next()`` runs: one sampler
+    serves every update.
+
+    Reading ``epoch`` or ``batch`` copies the word to the host, **a host sync**; setting either is an ordinary
+    stream-ordered write (a ``RuntimeError`` while capturing: the write would be recorded, not made).  Partial last
+    minibatches are not supported: ``DeviceRollout.get`` keeps them."""
+
+    def __init__(self, rollout, batch_size, seed=0):
+        B, M = int(batch_size), rollout.n_steps * rollout.n
+        if B <= 0 or B >= 2 ** 31 or M % B != 0:
+            raise ValueError(f"batch_size must be in [1, 2^31) and divide n_steps * num_envs = {M}: a recorded "
+                             f"minibatch has one shape")
+        if M // B >= 2 ** 32:
+            raise ValueError("more than 2^32 - 1 minibatches an epoch")
+        self.rollout, self.batch_size, self.batches_per_epoch = rollout, B, M // B
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.lib, self.device = rollout.lib, rollout.device
+        words = (int(self.lib.usv_rollout_cursor_bytes()) + 3) // 4
+        self._cursor = torch.zeros(words, dtype=torch.int32, device=self.device)    # epoch, batch, reserved
+
+    def _write(self, k, value, who):
+        from .optim import refuse_capture
+        refuse_capture(f"RolloutSampler.{who} was set", "set it between replays, outside the captured region")
+        _lib.word_write(self._cursor[k:k + 1], value)
+
+    @property
+    def epoch(self):
+        """The epoch of the next minibatch, a uint32 that wraps.  Reading it is a host sync."""
+        return _lib.word_read(self._cursor[0:1])
+
+    @epoch.setter
+    def epoch(self, value):
+        self._write(0, value, "epoch")
+
+    @property
+    def batch(self):
+        """The number of the next minibatch within its epoch.  Reading it is a host sync."""
+        return _lib.word_read(self._cursor[1:2])
+
+    @batch.setter
+    def batch(self, value):
+        if not 0 <= int(value) < self.batches_per_epoch:
+            raise ValueError(f"batch must be in [0, {self.batches_per_epoch})")
+        self._write(1, value, "batch")
+
+    def next(self, out=None, idx_out=None):
+        """The next minibatch as a ``RolloutSamples``, then the cursor moves on: one C call, two launches on the
+        current stream, no host sync, legal under capture.  ``out`` as ``DeviceRollout.gather``'s; ``idx_out``
+        (contiguous int64 [batch_size] on the device) receives the flat indices ``t * N + e`` of the samples."""
+        ro, B = self.rollout, self.batch_size
+        if idx_out is not None:
+            ro._check("idx_out", idx_out, torch.int64, (B,))
+        out = ro._out(B, out)
+        _lib.check(self.lib.usv_rollout_gather_perm(ro._rp, ro._fp, _ptr(self._cursor), self.seed, B, _ptr(idx_out),
+                                                    *(_ptr(t) for t in out), ro._stream()), self.lib)
+        return out
+
+    def state_dict(self):
+        """``{"seed", "epoch", "batch"}`` as Python ints (a host sync): what a checkpoint needs to go on with the
+        same sequence."""
+        e, b = (int(x) & 0xFFFFFFFF for x in self._cursor[:2].tolist())
+        return {"seed": self.seed, "epoch": e, "batch": b}
+
+    def load_state_dict(self, sd):
+        seed, batch = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF, int(sd["batch"])
+        if not 0 <= batch < self.batches_per_epoch:
+            raise ValueError(f"batch must be in [0, {self.batches_per_epoch})")
+        self.epoch, self.batch, self.seed = int(sd["epoch"]), batch, seed

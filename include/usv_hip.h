@@ -508,6 +508,28 @@ int usv_rollout_gather(const usv_rollout* ro, const usv_rollout_frames* fr, cons
                        float* obs_out, float* act_out, float* val_out, float* logp_out, float* adv_out,
                        float* ret_out, void* stream);
 
+/* The gather a HIP graph can replay: SB3's RolloutBuffer.get without a stored permutation.  Additive (ABI v5
+ * addition).  Which minibatch a call reads is not an argument, which a graph would freeze, but a cursor block in
+ * device memory: usv_rollout_cursor_bytes() bytes (16), 16-B aligned, uint32 epoch at byte 0 and uint32 batch at
+ * byte 4, the rest reserved; the caller zeroes it once and may write the two words between calls.
+ *
+ * usv_rollout_gather_perm(ro, fr, cursor_dev, seed, B, idx_out, out...), two launches and no sync, copy or
+ * allocation.  With M = n_steps * n: sample b < B of the call is i = perm_index(seed, epoch, M, batch * B + b), a
+ * bijection of [0, M) for every (seed, epoch): a six-round Feistel network over the next power of two (at least 4)
+ * with cycle walking, its round keys from Philox4x32-10 with key = seed and counter (epoch, "PERM", block, 0), a
+ * counter that the gSDE, CAPS and reset streams of the same seed never use (gym-usv_amd/csrc/usv_rollout_perm_math.hpp
+ * states it; tests/rollout_perm_ref.py restates it).  The outputs are usv_rollout_gather's at these indices, bit
+ * for bit; idx_out [B] int64, if not NULL, receives the indices.  Then one thread moves the cursor on: batch + 1,
+ * or (epoch + 1, 0) after the epoch's last minibatch; epoch wraps at 2^32.  M / B calls visit every sample once.
+ * A batch word that is not below M / B is read as 0.
+ *
+ * USV_ERR_ARG, before any HIP call, for B that does not divide M, a NULL or misaligned cursor block, an output
+ * that is the cursor block, a misaligned idx_out, and everything usv_rollout_gather refuses. */
+size_t usv_rollout_cursor_bytes(void);
+int usv_rollout_gather_perm(const usv_rollout* ro, const usv_rollout_frames* fr, void* cursor_dev, uint64_t seed,
+                            int32_t B, int64_t* idx_out, float* obs_out, float* act_out, float* val_out,
+                            float* logp_out, float* adv_out, float* ret_out, void* stream);
+
 /* Fused gSDE action head: SB3's StateDependentNoiseDistribution (common/distributions.py; full_std, no
  * expln, latent not learned through the noise) at rollout time, with the per-env exploration matrix rebuilt
  * from a counter-based generator in the launch that uses it instead of being stored.  Handle-free and
